@@ -28,6 +28,8 @@ batch_size_sweep (the mixed batch at 512 ... 16 384 ops) with predicted_strong_s
 this one GPU's step times), g16_table_radix / g16_table_bytes (which key tables produced `value`) and verification_c_abi (4096 Groth16 equality envelopes and 4096 range envelopes through the C ABI, and 65 536 equality envelopes through the one-pairing-check path).
 The timed region runs with the library's per-launch event profiling OFF; the launch durations behind `roofline` come from a second
 pass of the same K steps with it on (`profiled_pass` holds that pass's step time: the cost of the instrumentation is visible).
+--dump-outputs DIR writes what the last timed step computed (the packed proofs, lengths and status of rank 0's batch) as
+DIR/<name>.npy in float32 / float64, so that two builds can be compared output for output (dump_outputs).
 """
 import argparse
 import csv
@@ -124,6 +126,42 @@ def cpu_baseline(sample, threads):
                       "process_batch port, OpenMP %d threads, %.1f s wall = %.0f core-seconds" % (sample, sample // 4, threads, dt, dt * threads)}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(d, ops, out, off, st):
+    """--dump-outputs: what zkp_hip_batch_fetch hands a caller after the last timed step, as .npy files that two builds can compare.
+      proof_lengths.npy  float64 [n]  bytes of op i's proof (diff of the packed offsets)
+      status.npy         float32 [n]  per-op status code (0 = proved)
+      op_index.npy       float64 [k]  the ops whose proofs follow: every op when they fit, else a seeded sample (sorted)
+      proof_bytes.npy    float32 [*]  the proof bytes of those ops, concatenated in op order
+    The files stay under 64 MB: the sample is drawn from a fixed seed and sized by each op's upper bound (not its actual
+    length), so the same ops are chosen whatever the build computes."""
+    import numpy as np
+    from libzkp_amd import workloads as wl
+    n = len(ops)
+    off = off.astype(np.int64)
+    lens = np.diff(off)
+    room = (DUMP_BUDGET_BYTES - 4096 - 20 * n) // 4           # float32 proof bytes left after lengths, status, index and the headers
+    if int(off[n]) <= room:
+        idx = np.arange(n)
+    else:
+        bound = np.array([wl.max_output_bytes(ops[i:i + 1]) for i in range(n)], dtype=np.int64)
+        perm = np.random.default_rng(DUMP_SAMPLE_SEED).permutation(n)
+        k = int(np.searchsorted(np.cumsum(bound[perm]), room, side="right"))
+        idx = np.sort(perm[:k])
+    sel = np.concatenate([out[off[i]:off[i + 1]] for i in idx]) if len(idx) else np.zeros(0, dtype=np.uint8)
+    os.makedirs(d, exist_ok=True)
+    arrays = {"proof_lengths": lens.astype(np.float64), "status": st.astype(np.float32), "op_index": idx.astype(np.float64),
+              "proof_bytes": sel.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    total = sum(os.path.getsize(os.path.join(d, name + ".npy")) for name in arrays)
+    assert total <= DUMP_BUDGET_BYTES, total
+    return {"dir": d, "ops": n, "ops_with_bytes": int(len(idx)), "bytes_on_disk": total}
+
+
 def alone_durations():
     """Average duration of a kernel with every dispatch serialised (profiles/r03_kernel_alone.csv, written by tools/kernel_alone.py from the
     counter pass of tools/profile_round.sh): what the kernel takes when it has the GPU to itself."""
@@ -188,8 +226,11 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed and run the gather path even at world size 1 (tests/test_gpu_rccl.py)")
     ap.add_argument("--c5-batch", type=int, default=C5_BATCH, help="ops of the strong-scaling leg's one batch")
     ap.add_argument("--cpu-sample", type=int, default=1024)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy")
     ap.add_argument("--child-in-library", default="", help=argparse.SUPPRESS)       # internal: the in_library_shards leg (a comma-separated device list)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.child_in_library:
         return in_library_child([int(x) for x in args.child_in_library.split(",")], args.c5_batch, args.steps)
@@ -314,6 +355,11 @@ def main():
         G.drain()
     barrier()
     dt, step_ms = timed_steps(args.steps)                            # the timed region: no instrumentation inside the library
+    dumped = None
+    if args.dump_outputs and rank == 0:                              # outside the clock, before anything else runs on the batch
+        d_out = np.zeros(cap, dtype=np.uint8); d_off = np.zeros(n + 1, dtype=np.uint64); d_st = np.zeros(n, dtype=np.int32)
+        _native.check(L.zkp_hip_batch_fetch(h, P(d_out), cap, P(d_off), P(d_st)), "zkp_hip_batch_fetch (dump)")
+        dumped = dump_outputs(args.dump_outputs, ops, d_out, d_off, d_st)
 
     # second pass, same K steps, with an event pair around every MSM launch: the launch durations behind `roofline`
     L.zkp_hip_profile_enable(1)
@@ -586,6 +632,8 @@ def main():
                                      "valu_frac": (ed[2] * MADS_PER_ED_MADD / (ed[0] * 1e-3) / 1e12 / MAD_ISSUE_T) if ed[0] > 0 else None}},
         }
         res.update(extra)
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline and not args.force_dist:      # the contract: rank 0 at N = 1 only
             threads = min(len(os.sched_getaffinity(0)), 32)
             try:
