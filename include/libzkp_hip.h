@@ -41,8 +41,8 @@ enum {
 
 /* One-time setup on HIP device `device`: derives the 130 Bulletproofs generators (PedersenGens::default,
  * BulletproofGens::new party 0; replaces bp_gens_pair_bits, bulletproofs.rs:61-80), builds the
- * fixed-base window tables on the device (radix 2^16: 8.7 GB of HBM per GPU, self-checked slot against slot; plus 208 MB of radix-1024
- * tables for the verifier).  Idempotent.  Called implicitly (device 0) by the prove calls.
+ * fixed-base window tables on the device (radix 2^16: 8.7 GB of HBM per GPU, self-checked slot against slot; the verifier uses the
+ * same tables).  Idempotent.  Called implicitly (device 0) by the prove calls.
  * Every device initialised this way becomes one SHARD of the library (numbered in registration order). */
 int zkp_hip_init(int device);
 /* Multi-GPU (replaces the rayon fan-out of batch.rs:123-131 at node scale): registers `count` shards, shard k on
@@ -106,7 +106,7 @@ int zkp_hip_prove_consistency_batch(uint64_t n, const uint64_t* data, const uint
  * `{prefix}_pk.bin` key files (snark.rs:31-38,97-112).  Builds the fixed-base tables of every key point on the GPU. */
 int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len);
 /* What the loaded key of `kind` holds on the calling thread's shard: the radix of its fixed-base window tables (2^*wbits; *uneven = 1:
- * the 18-window form of radix 2^14) and the HBM they occupy (shared by the shards of one GPU).  Default policy: radix 2^13, ~34 GB for
+ * the 18-window form of radix 2^14) and the HBM they occupy (shared by the shards of one GPU).  Default policy: radix 2^13, ~27.8 GB for
  * the two circuits together; ZKP_HIP_G16_TABLE_BUDGET_MB=<MB per key> opts into larger tables (2^14-uneven, ~72 GB, measured 1.7 %
  * faster on the mixed batch), ZKP_HIP_G16_WBITS=8..15 forces a radix; a device with less free memory gets a smaller radix.  The
  * reference keeps a ProvingKey in host memory (snark.rs:40-56); this is the device-side cost of its replacement.  Any pointer may be NULL. */
@@ -238,11 +238,10 @@ void zkp_hip_profile_enable(int on);
 enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_KERNEL_MSM_BN254_G2 = 2 };
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset);
 int zkp_hip_profile_read(double* msm_ms, uint64_t* msm_launches, uint64_t* msm_point_adds, int reset);
-/* Tunables (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned
- * chunks of 32*T windows; 10000 + c = the window-granular layout with about c chunks.  sub-batches: independent slices
- * of a range batch on separate HIP streams (default 1: measured slower; takes effect at the next
- * zkp_hip_init).  msm variant: values >= 100 scale the resident-workgroup count the chunk choice aims at (x100). */
+/* Tunable (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned
+ * chunks of 32*T windows; 10000 + c = the window-granular layout with about c chunks. */
 void zkp_hip_set_window_budget(uint32_t budget);
+/* Kept for ABI compatibility; they have no effect. */
 void zkp_hip_set_subbatches(uint32_t n);
 void zkp_hip_set_msm_variant(uint32_t v);
 

@@ -31,7 +31,6 @@ struct G16Run {
     // recorded behind the final assembly of the last run on this workspace: the next run (possibly on another stream -- a per-variant
     // call while an asynchronous batch is in flight) waits for it before it overwrites z / digits / partials
     hipEvent_t last = nullptr; bool used = false;
-    hipStream_t sidem = nullptr, side2m = nullptr;        // the side streams confined to the Groth16 CU partition of a mixed batch (batch_impl.inc)
 };
 struct G16State {
     G16Key key[2];
@@ -121,14 +120,11 @@ uint32_t choose_chunks(uint64_t windows, uint32_t ntargets, uint32_t rows, uint3
     }
     return best;
 }
-// `part` selects the targets of the launch: G16_PART_ALL, or for G1 the two launches of the split pipeline (run_g16):
+// `part` selects the targets of the launch: G16_PART_ALL (G2), or for G1 the two launches of the split pipeline (run_g16):
 // G16_PART_AB = A and B1 (scalars z only, ready after the witness step), G16_PART_C = the l / h sum (needs the QAP step).
 enum { G16_PART_ALL = 0, G16_PART_AB = 1, G16_PART_C = 2 };
 int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chunking** out) {
-    // workgroups the chip holds at a time; ZKP_HIP_G16_FILL (percent, tuning knob) sizes the grids for a part of them, which
-    // leaves the rest of the CUs to the other variants' kernels of a mixed batch for the whole launch
-    static const int fill = env_int("ZKP_HIP_G16_FILL", 100);
-    const uint32_t resident = (uint32_t)(dev().cus_now ? dev().cus_now : dev().num_cu) * g16_msm_blocks_per_cu(g2) * (uint32_t)(fill < 10 ? 10 : fill > 100 ? 100 : fill) / 100u;
+    const uint32_t resident = (uint32_t)dev().num_cu * g16_msm_blocks_per_cu(g2);      // workgroups the chip holds at a time
     const auto& all = g2 ? K.targets_g2 : K.targets_g1;
     std::vector<SlotList> targets;
     if (part == G16_PART_ALL) targets = all;
@@ -136,10 +132,6 @@ int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chun
     else targets.assign(all.begin() + 2, all.end());
     uint64_t windows = 0; for (auto& t : targets) for (auto& sl : t) windows += sl.second;
     uint32_t c = choose_chunks(windows, (uint32_t)targets.size(), rows, resident, g16_msm_rows_per_block(g2));
-    // Rounds per launch (tuning knob): r > 1 cuts the grid into r times as many, r times shorter workgroups, so that workgroup
-    // slots free up throughout the launch and the other variants' kernels of a mixed batch get onto the CUs between them.
-    static const int rounds = env_int("ZKP_HIP_G16_ROUNDS", 1);
-    if (rounds > 1 && (uint64_t)c * rounds <= windows / 4 && c * rounds < 60000u) c *= (uint32_t)rounds;
     if (g_budget_request >= 10000) c = g_budget_request - 10000;                  // benchmarking knob
     auto& cache = g2 ? K.lays_g2 : K.lays_g1;
     const uint64_t key = (uint64_t)part << 32 | c;
@@ -565,30 +557,24 @@ int launch_msm_key(bool g2, const G16Radix& rx, const G16Key::Chunking& ch, cons
 // the batched prover for `rows` valid ops of one circuit kind; all pointers are device pointers
 
 int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_set_vals, const uint32_t* d_set_len, const uint8_t* d_seeds,
-            uint8_t* d_out, uint64_t stride, hipStream_t st, uint32_t lane = 0, bool masked = false, int phase = 0) {
-    // phase: 0 = the whole prover; 1 = only its head (witness + z digits: the start of the longest dependency chain of a circuit);
-    // 2 = everything after the head.  The mixed-batch scheduler enqueues the heads of both circuits BEFORE the ~50 launches of the
-    // Bulletproofs chain and the rest after them, so that the host's enqueue time of that chain (~0.25 ms) is not added to the chains
-    // that end the Groth16 phase.
+            uint8_t* d_out, uint64_t stride, hipStream_t st, uint32_t lane = 0) {
     G16Key& K = g16s().key[kind];
     if (!K.loaded) return fail(ZKP_HIP_E_ARGUMENT, "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
     const uint32_t nsc = g16_nscalars(K.nv, K.m);
-    // Split pipeline (default) -- the steps of one batch in dependency order on three streams, so that the latency-bound ones
+    // The steps of one batch in dependency order on three streams, so that the latency-bound ones
     // (QAP, partial sums, the two scalar multiplications) sit beside an MSM instead of between two:
     //   st    : witness, z digits | MSM A,B1 | MSM B2 (G2) -> sum |                       final
     //   side  :                   | QAP (h digits) -> MSM l,h -> sum --------------------- ^
     //   side2 :                              | sums of A, B1 -> s*A, r*B1 -----------------^
-    // ZKP_HIP_G16_SPLIT=0: the one-launch G1 MSM after the QAP step (A/B knob).
-    static const bool split = env_int("ZKP_HIP_G16_SPLIT", 1) != 0;
     const G16Key::Chunking *c1 = nullptr, *c1c = nullptr, *c2 = nullptr;
     int rc;
-    if ((rc = get_chunking(K, false, split ? G16_PART_AB : G16_PART_ALL, rows, &c1)) || (rc = get_chunking(K, true, G16_PART_ALL, rows, &c2))) return rc;
-    if (split && (rc = get_chunking(K, false, G16_PART_C, rows, &c1c))) return rc;
+    if ((rc = get_chunking(K, false, G16_PART_AB, rows, &c1)) || (rc = get_chunking(K, true, G16_PART_ALL, rows, &c2))) return rc;
+    if ((rc = get_chunking(K, false, G16_PART_C, rows, &c1c))) return rc;
     size_t off = 0;
     auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const size_t W = (size_t)32 * rows;
     const size_t o_z = sz(W * K.nv), o_sd = sz((size_t)K.rx.digw * 4 * rows * nsc), o_rs = sz(W * 2), o_p1 = sz((size_t)c1->lay.nchunks * G1_JAC_W * 4 * rows),
-                 o_p1c = sz(split ? (size_t)c1c->lay.nchunks * G1_JAC_W * 4 * rows : 0), o_p2 = sz((size_t)c2->lay.nchunks * G2_JAC_W * 4 * rows),
+                 o_p1c = sz((size_t)c1c->lay.nchunks * G1_JAC_W * 4 * rows), o_p2 = sz((size_t)c2->lay.nchunks * G2_JAC_W * 4 * rows),
                  o_s1 = sz((size_t)3 * G1_JAC_W * 4 * rows), o_s2 = sz((size_t)G2_JAC_W * 4 * rows), o_t1 = sz((size_t)G16_CPARTS * G1_JAC_W * 4 * rows),
                  o_qe = sz((size_t)2 * 9 * K.m * 4 * rows);
     G16Run& RW = g16s().run[kind][lane & 1u];
@@ -607,7 +593,7 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
         HIP_TRY(hipEventCreateWithFlags(&RW.last, hipEventDisableTiming));
     }
     G16Run& R0 = g16s().run[kind][0];          // the side streams are lane 0's for both lanes (see ensure_sub, zkp_hip.hip)
-    if (!masked && !R0.side) {
+    if (!R0.side) {
         // The runtime multiplexes streams onto four hardware queues per priority level, and two streams on one queue run one after the
         // other (traced in round 2: the G2 MSM of a circuit queued behind its own k_g16_cparts).  With the lanes' streams created on
         // demand (batch_impl.inc) a shard proving one batch at a time has four streams of the least priority -- equality and
@@ -618,59 +604,35 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
         HIP_TRY(hipStreamCreateWithPriority(&R0.side, hipStreamNonBlocking, stream_priority(side_level)));
         HIP_TRY(hipStreamCreateWithPriority(&R0.side2, hipStreamNonBlocking, stream_priority(side2_level)));
     }
-    if (masked && !R0.sidem) { if ((rc = make_masked_stream(&R0.sidem, false)) || (rc = make_masked_stream(&R0.side2m, false))) return rc; }
-    hipStream_t const side = masked ? R0.sidem : R0.side, side2 = masked ? R0.side2m : R0.side2;
+    hipStream_t const side = R0.side, side2 = R0.side2;
     hipEvent_t ev_wit = RW.ev[0], ev_ab = RW.ev[1], ev_c = RW.ev[2], ev_cp = RW.ev[3];
     ReduceView R2{}; R2.rows = rows; R2.ntargets = 1; R2.partial = p2; R2.target_chunk_begin = c2->lay.target_chunk_begin; R2.corr = c2->corr;
-    if (phase != 2) {
-        if (RW.used) HIP_TRY(hipStreamWaitEvent(st, RW.last, 0));
-        ZKP_TRACED("k_g16_witness", st, g16_launch_witness(V, st));
-        ZKP_TRACED("k_g16_zdigits", st, g16_launch_zdigits(V, st));
-        if (phase == 1) { HIP_TRY(hipGetLastError()); return 0; }
-    }
-    if (split) {
-        HIP_TRY(hipEventRecord(ev_wit, st));
-        // side: h, then the l / h part of C
-        HIP_TRY(hipStreamWaitEvent(side, ev_wit, 0));
-        { TraceMark tm_("k_g16_qap", side); HIP_TRY(g16_launch_qap(V, K.C, side)); }
-        if ((rc = launch_msm_key(false, K.rx, *c1c, K.table_g1, K.init_g1, rows, V.sdig, p1c, side))) return rc;
-        ReduceView Rc{}; Rc.rows = rows; Rc.ntargets = 1; Rc.partial = p1c; Rc.target_chunk_begin = c1c->lay.target_chunk_begin; Rc.corr = c1c->corr;
-        ZKP_TRACED("k_sum_t<G1Msm>", side, g16_launch_sum(false, Rc, s1 + (size_t)2 * G1_JAC_W * rows, side));
-        HIP_TRY(hipEventRecord(ev_c, side));
-        // st: A and B1, whose sums the scalar multiplications on side2 wait for, then B2
-        if ((rc = launch_msm_key(false, K.rx, *c1, K.table_g1, K.init_g1, rows, V.sdig, p1, st))) return rc;
-        ReduceView Rab{}; Rab.rows = rows; Rab.ntargets = 2; Rab.partial = p1; Rab.target_chunk_begin = c1->lay.target_chunk_begin; Rab.corr = c1->corr;
-        // The partial sums of A / B1 feed only the scalar multiplications: they go to side2 with them, so that the G2 MSM -- which needs
-        // neither -- follows the G1 MSM directly instead of queueing behind a latency-bound kernel that waits for registers beside the other
-        // streams' gather waves (traced: 0.8-3.9 ms for a 0.2 ms kernel).  ZKP_HIP_G16_SUM_ON_MAIN=1: the sums on st, as before round 4.
-        static const bool sum_on_main = env_int("ZKP_HIP_G16_SUM_ON_MAIN", 0) != 0;
-        if (sum_on_main) ZKP_TRACED("k_sum_t<G1Msm>", st, g16_launch_sum(false, Rab, s1, st));
-        HIP_TRY(hipEventRecord(ev_ab, st));
-        HIP_TRY(hipStreamWaitEvent(side2, ev_ab, 0));
-        if (!sum_on_main) ZKP_TRACED("k_sum_t<G1Msm>", side2, g16_launch_sum(false, Rab, s1, side2));
-        ZKP_TRACED("k_g16_cparts", side2, g16_launch_cparts(V, s1, t1, side2));
-        HIP_TRY(hipEventRecord(ev_cp, side2));
-        if ((rc = launch_msm_key(true, K.rx, *c2, K.table_g2, K.init_g2, rows, V.sdig, p2, st))) return rc;
-        ZKP_TRACED("k_sum_t<G2Msm>", st, g16_launch_sum(true, R2, s2, st));
-        HIP_TRY(hipStreamWaitEvent(st, ev_c, 0));
-        HIP_TRY(hipStreamWaitEvent(st, ev_cp, 0));
-    } else {
-        HIP_TRY(g16_launch_qap(V, K.C, st));
-        if ((rc = launch_msm_key(false, K.rx, *c1, K.table_g1, K.init_g1, rows, V.sdig, p1, st))) return rc;
-        ReduceView R1{}; R1.rows = rows; R1.ntargets = 3; R1.partial = p1; R1.target_chunk_begin = c1->lay.target_chunk_begin; R1.corr = c1->corr;
-        g16_launch_sum(false, R1, s1, st);
-        // s*A and r*B1 (two 254-bit double-and-add chains per proof, 2 x rows lanes: a latency-bound kernel on a fraction of the
-        // SIMDs) need only the G1 sums: they run on a side stream beside the G2 MSM and join before the final assembly.
-        // (Tried: that side stream CU-masked.  The G2 workgroups fill whole CUs and are dealt evenly over shader engines, so
-        // masking CUs out of some engines doubled the MSM time; DESIGN.md 6b.)
-        HIP_TRY(hipEventRecord(ev_ab, st));
-        HIP_TRY(hipStreamWaitEvent(side2, ev_ab, 0));
-        g16_launch_cparts(V, s1, t1, side2);
-        HIP_TRY(hipEventRecord(ev_cp, side2));
-        if ((rc = launch_msm_key(true, K.rx, *c2, K.table_g2, K.init_g2, rows, V.sdig, p2, st))) return rc;
-        g16_launch_sum(true, R2, s2, st);
-        HIP_TRY(hipStreamWaitEvent(st, ev_cp, 0));
-    }
+    if (RW.used) HIP_TRY(hipStreamWaitEvent(st, RW.last, 0));
+    ZKP_TRACED("k_g16_witness", st, g16_launch_witness(V, st));
+    ZKP_TRACED("k_g16_zdigits", st, g16_launch_zdigits(V, st));
+    HIP_TRY(hipEventRecord(ev_wit, st));
+    // side: h, then the l / h part of C
+    HIP_TRY(hipStreamWaitEvent(side, ev_wit, 0));
+    { TraceMark tm_("k_g16_qap", side); HIP_TRY(g16_launch_qap(V, K.C, side)); }
+    if ((rc = launch_msm_key(false, K.rx, *c1c, K.table_g1, K.init_g1, rows, V.sdig, p1c, side))) return rc;
+    ReduceView Rc{}; Rc.rows = rows; Rc.ntargets = 1; Rc.partial = p1c; Rc.target_chunk_begin = c1c->lay.target_chunk_begin; Rc.corr = c1c->corr;
+    ZKP_TRACED("k_sum_t<G1Msm>", side, g16_launch_sum(false, Rc, s1 + (size_t)2 * G1_JAC_W * rows, side));
+    HIP_TRY(hipEventRecord(ev_c, side));
+    // st: A and B1, whose sums the scalar multiplications on side2 wait for, then B2
+    if ((rc = launch_msm_key(false, K.rx, *c1, K.table_g1, K.init_g1, rows, V.sdig, p1, st))) return rc;
+    ReduceView Rab{}; Rab.rows = rows; Rab.ntargets = 2; Rab.partial = p1; Rab.target_chunk_begin = c1->lay.target_chunk_begin; Rab.corr = c1->corr;
+    // The partial sums of A / B1 feed only the scalar multiplications: they go to side2 with them, so that the G2 MSM -- which needs
+    // neither -- follows the G1 MSM directly instead of queueing behind a latency-bound kernel that waits for registers beside the other
+    // streams' gather waves (traced: 0.8-3.9 ms for a 0.2 ms kernel).
+    HIP_TRY(hipEventRecord(ev_ab, st));
+    HIP_TRY(hipStreamWaitEvent(side2, ev_ab, 0));
+    ZKP_TRACED("k_sum_t<G1Msm>", side2, g16_launch_sum(false, Rab, s1, side2));
+    ZKP_TRACED("k_g16_cparts", side2, g16_launch_cparts(V, s1, t1, side2));
+    HIP_TRY(hipEventRecord(ev_cp, side2));
+    if ((rc = launch_msm_key(true, K.rx, *c2, K.table_g2, K.init_g2, rows, V.sdig, p2, st))) return rc;
+    ZKP_TRACED("k_sum_t<G2Msm>", st, g16_launch_sum(true, R2, s2, st));
+    HIP_TRY(hipStreamWaitEvent(st, ev_c, 0));
+    HIP_TRY(hipStreamWaitEvent(st, ev_cp, 0));
     ZKP_TRACED("k_g16_final", st, g16_launch_final(V, s1, s2, t1, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(RW.last, st)); RW.used = true;
@@ -728,7 +690,6 @@ void g16_release_all() {
     for (auto& circuit : S->run) for (auto& W : circuit) {
         if (W.side) { (void)hipStreamDestroy(W.side); (void)hipStreamDestroy(W.side2); }
         if (W.last) { for (auto e : W.ev) (void)hipEventDestroy(e); (void)hipEventDestroy(W.last); }
-        if (W.sidem) { (void)hipStreamDestroy(W.sidem); (void)hipStreamDestroy(W.side2m); }
         if (W.buf) (void)hipFree(W.buf);
     }
     for (auto& K : S->key) {

@@ -302,8 +302,6 @@ struct Device {
     uint64_t generation = 0;            // bumped by zkp_hip_shutdown: staged batches of an earlier life own nothing any more
     int num_cu = 256;
     int msm_prio_now = 0;               // set by the mixed-batch scheduler while it enqueues the Bulletproofs chain of a batch that also holds Groth16 work: the ed25519 MSM waves raise their issue priority
-    int cus_now = 0;                    // CUs the launches being enqueued may use (0 = all): set by the mixed-batch scheduler while it enqueues a variant on CU-masked streams
-    std::vector<SubBatch> subm;         // [lane]: Bulletproofs streams + workspace confined to the Bulletproofs CU partition of a mixed batch
     hipStream_t stream = nullptr;
     uint32_t* d_edg_table = nullptr;    // radix-2^16 tables, gathered per lane from HBM (edg.h: every MSM of the prover)
     int edg_blocks_per_cu = 3;
@@ -313,8 +311,8 @@ struct Device {
     Family fam[4];
     LayoutSet p2, ct;
     uint32_t max_chunks = 0;
-    std::vector<SubBatch> sub;          // [slot * nsub + h]
-    uint32_t nsub = 1, next_slot = 0;
+    SubBatch sub[NSLOTS];               // [slot]
+    uint32_t next_slot = 0;
     DevPool pool;
     // the other parts of the library keep their per-shard state behind these (created on first use, freed by shutdown)
     G16State* g16 = nullptr; StarkState* stark = nullptr; VfyState* vfy = nullptr; BatchState* batch = nullptr;
@@ -377,8 +375,6 @@ Device& dev() { return *t_dev; }
 DevPool& dev_pool() { return dev().pool; }
 void dev_scope_quiesce() { if (dev().stream) (void)hipStreamSynchronize(dev().stream); }
 uint32_t g_budget_request = 0;     // 0 = choose per launch
-double g_fill = 1.0;               // benchmarking knob: scales the resident-workgroup count the Bulletproofs MSM chunking aims at
-uint32_t g_subbatches = 1;         // >1: independent slices on separate streams (measured slower on MI355X: see DESIGN.md)
 // Stream priorities (mixed batches run their variants on separate streams).  0 = greatest priority of the device, 1 = default,
 // 2 = least.  What counts is the order: the Bulletproofs pipeline -- a chain of ~50 dependent launches, most of them short -- above
 // the Groth16 streams with their long MSM grids (4096-op mixed batch, same box: 13.8-13.9 ms with Bulletproofs above Groth16, 16.0 ms
@@ -530,14 +526,13 @@ const DevLayout& pick_layout(const LayoutSet& S, uint32_t rows) {
     }
     if (g_budget_request) { int T = (int)(g_budget_request / 32); if (T < 1) T = 1; if (T > MAXT) T = MAXT; return S.cand[T - 1]; }
     // Take the window-granular layout that minimises rounds x (windows per workgroup + per-workgroup overhead) + the partial-sum
-    // work that grows with the chunk count; g_fill scales the resident count (benchmarking knob, default 1).
-    static const int fill_pct = env_int("ZKP_HIP_BP_FILL", 100);      // tuning knob: size the MSM grids for this percentage of the CUs
+    // work that grows with the chunk count.
     // The gather launches run 256-lane workgroups of four independent waves, edg_blocks_per_cu of them per CU:
     // no strict rounds, but the same trade -- more chunks fill the chip and shorten a lane's chain of additions, and every chunk is one
     // more partial point per proof for k_sum_t (a 9-product addition against the 7 of a table step).
     const uint32_t tb = edg_msm_rows_per_block();
     const double per_cu = (double)dev().edg_blocks_per_cu;
-    const double resident = g_fill * (fill_pct / 100.0) * (double)(dev().cus_now ? dev().cus_now : dev().num_cu) * per_cu;
+    const double resident = (double)dev().num_cu * per_cu;
     const uint32_t groups = (rows + tb - 1) / tb;
     size_t best = MAXT; double best_cost = 1e300;
     for (size_t i = MAXT; i < S.cand.size(); i++) {
@@ -634,34 +629,14 @@ int init_device() {
     if ((rc = upload_set(D.ct, targets_ctask(EDG_NWIN, EDG_NWIN_U64)))) return rc;
     D.max_chunks = D.p2.max_chunks;
     if ((rc = ensure_family(6))) return rc;
-    uint32_t ns = g_subbatches; if (ns <= 1) ns = (uint32_t)env_int("ZKP_HIP_BP_SUBBATCHES", 1); if (ns < 1) ns = 1; if (ns > 8) ns = 8;
-    D.nsub = ns;
-    D.sub.resize((size_t)NSLOTS * ns);       // streams and events of a slot exist from its first use (ensure_sub)
     D.ready = true;
     return 0;
 }
-// ---- CU partition of a mixed batch (experiment, OFF by default: ZKP_HIP_BP_CUS = CUs per XCD for the Bulletproofs streams).  The
-// Bulletproofs prover is a chain of ~50 dependent launches whose MSM workgroups need whole CUs (1024 lanes, 120 KB of LDS) and whose
-// lane = proof kernels need 120-256 VGPRs; next to the Groth16 gather kernels (three 136-VGPR waves per SIMD, workgroups that live
-// 1.5-2.5 ms) each of those launches waits for workgroup slots (launch trace, round 3: first inner-product round reached at ~10 ms of a
-// 14 ms step, the last rounds then run on an idle GPU).  Giving each side its own CUs (hipExtStreamCreateWithCUMask; mask bit b = CU
-// b / 8 of XCD b mod 8, tools/cumask_probe.hip; every grid sized for its partition) removes the waiting but not the arithmetic: the
-// Bulletproofs MSMs are 2.2 ms of whole-GPU work, so on a quarter of the CUs the chain takes 12+ ms and the step 16.3-16.8 ms (8 or 12
-// CUs per XCD) against 13.7 ms unpartitioned on the same box; 6 and 10 CUs per XCD measured 21-27 ms.  Kept as a knob.
-int bp_cus_per_xcd() { static const int v = env_int("ZKP_HIP_BP_CUS", 0); return v < 0 ? 0 : v > 24 ? 24 : v; }
-int make_masked_stream(hipStream_t* out, bool bp_part) {
-    const int per_xcd = dev().num_cu / 8, nb = bp_cus_per_xcd();
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < per_xcd * 8 && b < 256; b++) if ((b < nb * 8) == bp_part) mask[b >> 5] |= 1u << (b & 31);
-    HIP_TRY(hipExtStreamCreateWithCUMask(out, 8, mask));
-    return 0;
-}
-int partition_cus(bool bp_part) { const int nb = bp_cus_per_xcd() * 8; return bp_part ? nb : dev().num_cu - nb; }
 // `share`: take the streams of that slot instead of creating a pair.  The second slot of a shard (the second of two batches in flight)
 // is a second workspace on the SAME streams: its chain queues behind the first batch's chain of the same variant, which is the overlap
 // one wants -- the tail of one batch under the head of the next -- without a second set of hardware queues (with its own streams the
 // second lane shared queues with the first one's, and two batches in flight measured slower than one: 15.1 against 13.6 ms per batch).
-int ensure_sub(SubBatch& sb, bool masked = false, SubBatch* share = nullptr) {
+int ensure_sub(SubBatch& sb, SubBatch* share = nullptr) {
     if (sb.stream) return 0;
     // Built in locals and committed to `sb` only when every object exists: a failure half-way (these are created lazily, in the middle of
     // a batch enqueue) must not leave a slot that looks ready but holds null events.
@@ -673,10 +648,8 @@ int ensure_sub(SubBatch& sb, bool masked = false, SubBatch* share = nullptr) {
     };
     int rc = 0;
     if (share && share != &sb) {
-        if ((rc = ensure_sub(*share, masked))) return rc;
+        if ((rc = ensure_sub(*share))) return rc;
         stream = share->stream; side = share->side; borrowed = true;
-    } else if (masked) {
-        if ((rc = make_masked_stream(&stream, true)) || (rc = make_masked_stream(&side, true))) { undo(); return rc; }
     } else {
         hipError_t e = hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, stream_priority(bp_priority_level()));
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, stream_priority(bp_priority_level()));
@@ -857,20 +830,16 @@ __global__ void k_any_failed(const int32_t* status, uint32_t n, int* flag) {
     if (i < n && status[i] != 0) atomicOr(flag, 1);
 }
 
-// Ops are independent, so the batch is cut into contiguous sub-batches that run the whole kernel sequence on their
-// own streams: while one sub-batch is in a latency-bound per-proof step (transcript, inversion, encoding) the other's
-// MSM keeps the CUs busy.  `st` (the caller's stream) is forked into the sub-streams and joined again.
+// The whole kernel sequence of the batch runs on the streams of one slot: `st` (the caller's stream) is forked into the slot's stream
+// and joined again.  (Cutting the batch into sub-batches on streams of their own measured slower: DESIGN.md.)
 int prove_range_device_locked(uint64_t n, const uint64_t* d_value, const uint64_t* d_min, const uint64_t* d_max, uint32_t lg,
                               const uint8_t* d_seeds, uint8_t* d_out, uint64_t stride, uint32_t* d_out_len, int32_t* d_status,
-                              hipStream_t st, int* any_failed, int slot_hint = -1, bool masked = false) {
+                              hipStream_t st, int* any_failed, int slot_hint = -1) {
     if (n == 0) { if (any_failed) *any_failed = 0; return 0; }
     { int rcn = check_batch_size(n); if (rcn) return rcn; }
     if (stride < range_envelope_bytes(lg)) return fail(ZKP_HIP_E_ARGUMENT, "stride is smaller than the proof (1478 bytes for n_bits = 64)");
     int rc;
     if ((rc = ensure_family(lg))) return rc;
-    uint32_t nsub = dev().nsub;
-    if (n < 512) nsub = 1;                       // small batches: one stream
-    const uint64_t per = (n + nsub - 1) / nsub;
     // slot (streams + workspace): the scheduler's lane when it calls; otherwise slot 0 unless a batch is still running there (a
     // caller that keeps two batches in flight from two of its own streams then gets both slots)
     uint32_t slot = 0;
@@ -880,35 +849,26 @@ int prove_range_device_locked(uint64_t n, const uint64_t* d_value, const uint64_
         if (s0.used && hipEventQuery(s0.done) == hipErrorNotReady) { slot = 1 + dev().next_slot % (NSLOTS - 1); dev().next_slot++; }
         (void)hipGetLastError();
     }
-    if (masked) {                                  // the scheduler's CU partition: one slice on the lane's masked streams
-        nsub = 1;
-        if (dev().subm.size() < NSLOTS) dev().subm.resize(NSLOTS);
-        if ((rc = ensure_sub(dev().subm[slot], true, &dev().subm[0]))) return rc;
-    } else for (uint32_t h = 0; h < dev().nsub; h++) if ((rc = ensure_sub(dev().sub[(size_t)slot * dev().nsub + h], false, &dev().sub[h]))) return rc;
-    SubBatch& first = masked ? dev().subm[slot] : dev().sub[(size_t)slot * dev().nsub];
-    HIP_TRY(hipEventRecord(first.start, st));
-    for (uint32_t h = 0; h < nsub; h++) {
-        const uint64_t lo = h * per, hi = (lo + per < n) ? lo + per : n;
-        if (lo >= hi) continue;
-        SubBatch& sb = masked ? dev().subm[slot] : dev().sub[(size_t)slot * dev().nsub + h];
-        const uint32_t C = (uint32_t)(hi - lo), M = 2 * C;
-        if ((rc = ensure_workspace(sb, M, C))) return rc;
-        Ws w; carve((uint8_t*)sb.ws, M, C, dev().max_chunks, &w);
-        w.V.n = 1u << lg; w.V.lg = lg;
-        w.V.seeds = reinterpret_cast<const uint32_t*>(d_seeds + 32 * lo); w.T.seeds = w.V.seeds;
-        w.V.out = d_out + lo * stride;
-        HIP_TRY(hipStreamWaitEvent(sb.stream, first.start, 0));        // (the slot's previous batch is ahead of this one on sb.stream)
-        if (sb.used) HIP_TRY(hipStreamWaitEvent(sb.stream, sb.done, 0));   // ... unless it was a host-described job list on another stream (run_jobs_on)
-        ZKP_TRACED("k_build_range", sb.stream, k_build_range<<<(C + TB - 1) / TB, TB, 0, sb.stream>>>(w.J, C, d_value + lo, d_min + lo, d_max + lo, lg, w.V.out, stride, d_out_len + lo, d_status + lo));
-        if ((rc = run_pipeline(w, M, C, sb.stream, sb))) return rc;
-        HIP_TRY(hipEventRecord(sb.done, sb.stream)); sb.used = true;
-        HIP_TRY(hipStreamWaitEvent(st, sb.done, 0));
-    }
+    SubBatch& sb = dev().sub[slot];
+    if ((rc = ensure_sub(sb, &dev().sub[0]))) return rc;
+    HIP_TRY(hipEventRecord(sb.start, st));
+    const uint32_t C = (uint32_t)n, M = 2 * C;
+    if ((rc = ensure_workspace(sb, M, C))) return rc;
+    Ws w; carve((uint8_t*)sb.ws, M, C, dev().max_chunks, &w);
+    w.V.n = 1u << lg; w.V.lg = lg;
+    w.V.seeds = reinterpret_cast<const uint32_t*>(d_seeds); w.T.seeds = w.V.seeds;
+    w.V.out = d_out;
+    HIP_TRY(hipStreamWaitEvent(sb.stream, sb.start, 0));           // (the slot's previous batch is ahead of this one on sb.stream)
+    if (sb.used) HIP_TRY(hipStreamWaitEvent(sb.stream, sb.done, 0));   // ... unless it was a host-described job list on another stream (run_jobs_on)
+    ZKP_TRACED("k_build_range", sb.stream, k_build_range<<<(C + TB - 1) / TB, TB, 0, sb.stream>>>(w.J, C, d_value, d_min, d_max, lg, w.V.out, stride, d_out_len, d_status));
+    if ((rc = run_pipeline(w, M, C, sb.stream, sb))) return rc;
+    HIP_TRY(hipEventRecord(sb.done, sb.stream)); sb.used = true;
+    HIP_TRY(hipStreamWaitEvent(st, sb.done, 0));
     if (any_failed) {
-        Ws w; carve((uint8_t*)first.ws, first.capM, first.capC, dev().max_chunks, &w);
-        HIP_TRY(hipMemsetAsync(w.flag, 0, sizeof(int), st));
-        k_any_failed<<<(uint32_t)((n + TB - 1) / TB), TB, 0, st>>>(d_status, (uint32_t)n, w.flag);
-        HIP_TRY(hipMemcpyAsync(any_failed, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        Ws wf; carve((uint8_t*)sb.ws, sb.capM, sb.capC, dev().max_chunks, &wf);
+        HIP_TRY(hipMemsetAsync(wf.flag, 0, sizeof(int), st));
+        k_any_failed<<<(uint32_t)((n + TB - 1) / TB), TB, 0, st>>>(d_status, (uint32_t)n, wf.flag);
+        HIP_TRY(hipMemcpyAsync(any_failed, wf.flag, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
@@ -1049,8 +1009,8 @@ extern "C" {
 
 const char* zkp_hip_last_error(void) { return t_err.c_str(); }
 void zkp_hip_set_window_budget(uint32_t budget) try { g_budget_request = budget; } ZKP_API_CATCH_VOID
-void zkp_hip_set_subbatches(uint32_t n) try { g_subbatches = n; } ZKP_API_CATCH_VOID
-void zkp_hip_set_msm_variant(uint32_t v) try { if (v >= 100) g_fill = v / 100.0; } ZKP_API_CATCH_VOID   // benchmarking knob: grid fill target x100 (single kernel variant remains)
+void zkp_hip_set_subbatches(uint32_t) {}      // kept for ABI compatibility: no effect
+void zkp_hip_set_msm_variant(uint32_t) {}
 
 int zkp_hip_init(int device) try {
     Device* d = nullptr;
@@ -1124,16 +1084,14 @@ void zkp_hip_shutdown(void) try {
         bpv_release_all();
         stark_release_all();
         d->pool.release_all();
-        for (auto* vec : {&d->sub, &d->subm}) {
-            for (auto& sb : *vec) {
-                if (sb.ws) (void)hipFree(sb.ws);
-                if (!sb.stream) continue;
+        for (auto& sb : d->sub) {
+            if (sb.ws) (void)hipFree(sb.ws);
+            if (sb.stream) {
                 if (!sb.borrowed) { (void)hipStreamDestroy(sb.stream); (void)hipStreamDestroy(sb.side); }
                 (void)hipEventDestroy(sb.start); (void)hipEventDestroy(sb.done); (void)hipEventDestroy(sb.side_go); (void)hipEventDestroy(sb.side_done);
             }
-            vec->clear();
+            sb = SubBatch();
         }
-        d->cus_now = 0;
         d->msm_prio_now = 0;
         release_edg_table();
         free_set(d->p2); free_set(d->ct);
