@@ -8,16 +8,12 @@ struct EdGather {      // edwards25519, affine-Niels entries gathered per lane f
     static __device__ __forceinline__ int32_t digit(uint32_t word, uint32_t w) { return (int32_t)(int16_t)(word >> (16 * (w & 1u))); }
     using Acc = ge;
     static __device__ __forceinline__ Acc identity() { return ge_identity(); }
-#ifndef ZKP_EDG_WAVES
-#define ZKP_EDG_WAVES 3
-#define ZKP_EDG_PREFETCH 2
-#endif
     // Three waves per SIMD with the entries of the next TWO steps in flight (2 x 24 registers, 155 VGPRs, no spills).  Measured (MI355X, 4096 x
     // prove_range staged, ms per batch): four waves and no lead 11.7 -- the 128-register budget leaves no room for an entry in flight and the
     // gather's latency shows on every step --, four waves with one step of lead (64 spilled registers) 11.5, four waves with the lead through
     // LDS by DMA 7.9, three waves with one step of lead 7.4, with two 7.5 (mixed batch: 12.6 / 12.4); the LDS-streamed radix-1024 kernel
     // this replaces: 9.6 (profiles/r04_edg_ab.jsonl)
-    static constexpr uint32_t GATHER_WAVES = ZKP_EDG_WAVES; static constexpr int GATHER_PREFETCH = ZKP_EDG_PREFETCH;
+    static constexpr uint32_t GATHER_WAVES = 3; static constexpr int GATHER_PREFETCH = 2;
     static constexpr uint32_t GATHER_W = EDG_ENTRY_W, GATHER_STRIDE = EDG_SLOT_W, GATHER_PRIO = 0;
     using GAcc = ge;
     static __device__ __forceinline__ GAcc to_gather(const ge& a) { return a; }
@@ -30,10 +26,7 @@ struct EdGather {      // edwards25519, affine-Niels entries gathered per lane f
 template __global__ void k_msm_gather<EdGather>(MsmView, uint32_t, uint32_t);
 // The same kernel with its waves' issue priority raised (s_setprio; levels 1, 2 and 3 measured alike): for the chain's launches in a batch
 // that also holds Groth16 work, whose G1 / G2 gather waves share the SIMDs (batch_impl.inc).
-#ifndef ZKP_EDG_PRIO
-#define ZKP_EDG_PRIO 1
-#endif
-struct EdGatherPrio : EdGather { static constexpr uint32_t GATHER_PRIO = ZKP_EDG_PRIO; };
+struct EdGatherPrio : EdGather { static constexpr uint32_t GATHER_PRIO = 1; };
 template __global__ void k_msm_gather<EdGatherPrio>(MsmView, uint32_t, uint32_t);
 
 uint32_t edg_msm_rows_per_block() { return 256; }

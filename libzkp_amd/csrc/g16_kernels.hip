@@ -7,11 +7,7 @@ struct G1Msm {      // BN254 G1 key points (Groth16 a / b1 / h / l queries): pac
     static __device__ __forceinline__ int32_t digit(uint32_t word, uint32_t w) { return (int32_t)(int16_t)(word >> (16 * (w & 1u))); }
     using Acc = g1_jac;
     static __device__ __forceinline__ Acc identity() { return jac_infinity<fq>(); }
-#ifndef ZKP_G1_GATHER_WAVES
-#define ZKP_G1_GATHER_WAVES 3
-#define ZKP_G1_GATHER_PREFETCH 2
-#endif
-    static constexpr uint32_t GATHER_WAVES = ZKP_G1_GATHER_WAVES; static constexpr int GATHER_PREFETCH = ZKP_G1_GATHER_PREFETCH;      // k_msm_gather: 3 waves/SIMD, entries two steps ahead
+    static constexpr uint32_t GATHER_WAVES = 3; static constexpr int GATHER_PREFETCH = 2;      // k_msm_gather: 3 waves/SIMD, entries two steps ahead
     // the gather loop accumulates in XYZZ coordinates on nine 29-bit limbs (bn254_g.h: g1_mmadd9); the key tables hold the
     // nine-limb coordinates packed into eight words each (fq9_pack8): a 64-byte, 64-byte-aligned entry x | y (k_g16_build_table)
     static constexpr uint32_t GATHER_W = 16, GATHER_STRIDE = 16, GATHER_PRIO = 0;
@@ -32,10 +28,7 @@ struct G2Msm {      // BN254 G2 (Fq2 coordinates), Groth16 b_g2_query
     static __device__ __forceinline__ int32_t digit(uint32_t word, uint32_t w) { return (int32_t)(int16_t)(word >> (16 * (w & 1u))); }
     using Acc = g2_jac;
     static __device__ __forceinline__ Acc identity() { return jac_infinity<fq2>(); }
-#ifndef ZKP_G2_GATHER_PREFETCH
-#define ZKP_G2_GATHER_PREFETCH (-1)
-#endif
-    static constexpr uint32_t GATHER_WAVES = 2; static constexpr int GATHER_PREFETCH = ZKP_G2_GATHER_PREFETCH;     // k_msm_gather: the addition itself takes ~240 VGPRs; entries one step ahead through LDS
+    static constexpr uint32_t GATHER_WAVES = 2; static constexpr int GATHER_PREFETCH = -1;     // k_msm_gather: the addition itself takes ~240 VGPRs; entries one step ahead through LDS
     // the gather loop: XYZZ coordinates over Fq2 on nine 29-bit limbs (bn254_g.h: g2_mmadd9); table entries are the four
     // coordinates x.c0, x.c1, y.c0, y.c1 packed into eight words each: 128 bytes, one cache line
     static constexpr uint32_t GATHER_W = 32, GATHER_STRIDE = 32, GATHER_PRIO = 0;

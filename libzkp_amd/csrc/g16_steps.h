@@ -20,9 +20,6 @@ namespace zkp {
 // scalar, 5 per 64-bit value -- then 2^13, 2^12, ... down to 2^8, 33 MB per circuit); ZKP_HIP_G16_WBITS forces one.  Measured on the
 // 4096-op mixed batch in round 2: radix 2^13 16.0 ms, 2^14 15.6 ms, 2^15 another ~1.5 % for 143 GB; the LDS-streamed radix-1024
 // tables of round 1 needed 26 additions per scalar.
-#ifndef ZKP_G16_WBITS
-#define ZKP_G16_WBITS 14
-#endif
 // Radix of a key's window tables.  Even form: nwin windows of wbits bits, nent = 2^(wbits-1) entries each (signed digits).  Uneven form
 // (wbits = 14 only): a 254-bit scalar in 18 windows instead of 19 -- at 19 x 14 bits the last window holds two bits and four of its 8192
 // entries are ever read -- as sixteen 14-bit windows, one 15-bit window (signed digits, 2 nent entries) and the top 15 bits (bits 239..253 of
@@ -40,7 +37,7 @@ ZKP_HD inline G16Radix g16_radix(uint32_t wbits, bool uneven = false) {
 ZKP_HD inline uint32_t g16_win_bit(const G16Radix& rx, uint32_t w) { return rx.uneven && w == 17 ? 239u : rx.wbits * w; }      // first bit of window w
 ZKP_HD inline uint32_t g16_win_off(const G16Radix& rx, uint32_t w) { return (w + (rx.uneven && w == 17 ? 1u : 0u)) * rx.nent; }  // first entry of window w in a base's block
 ZKP_HD inline uint32_t g16_win_ent(const G16Radix& rx, uint32_t w) { return !rx.uneven || w < 16 ? rx.nent : w == 16 ? 2u * rx.nent : G16_UNEVEN_TOP_ENT; }
-constexpr uint32_t G16_WBITS_DEFAULT = ZKP_G16_WBITS, G16_WBITS_KNEE = 13, G16_WBITS_MIN = 8, G16_WBITS_MAX = 15, G16_DIGW_MAX = 16;      // radix 2^8: 32 windows = 16 digit words
+constexpr uint32_t G16_WBITS_DEFAULT = 14, G16_WBITS_KNEE = 13, G16_WBITS_MIN = 8, G16_WBITS_MAX = 15, G16_DIGW_MAX = 16;      // radix 2^8: 32 windows = 16 digit words
 static_assert(G16_WBITS_DEFAULT >= G16_WBITS_MIN && G16_WBITS_DEFAULT <= G16_WBITS_MAX, "key-table radix out of range");
 // packed signed digits of a raw canonical scalar at the radix rx (packed[] holds G16_DIGW_MAX words; the first rx.digw are meaningful)
 ZKP_HD inline void g16_recode_uneven(uint32_t* packed, const sc& raw) {

@@ -45,13 +45,7 @@ __global__ void __launch_bounds__(256, T::GATHER_WAVES) k_msm_gather(MsmView m, 
     typename T::GAcc acc = T::to_gather(m.acc_init ? T::load(m.acc_init, 0, 0, 1) : T::identity());    // the coordinate system of the loop
     const uint4* const table4 = reinterpret_cast<const uint4*>(m.table);
     auto digit_word = [&](const uint2 ds) -> uint32_t { return active ? m.digits[(size_t)(ds.y >> 1) * m.rows + row] : 0u; };
-#if defined(ZKP_GATHER_EXPERIMENT) && ZKP_GATHER_EXPERIMENT == 1          // measurement builds only (tools/): every gather reads the table's first entry (always an L1 hit)
-    auto entry_of = [&](const uint2, int32_t) -> const uint4* { return table4; };
-#elif defined(ZKP_GATHER_EXPERIMENT) && ZKP_GATHER_EXPERIMENT == 2        // ... every lane of a wave reads the first entry of the step's window (one line per wave-step)
-    auto entry_of = [&](const uint2 ds, int32_t) -> const uint4* { return table4 + (uint64_t)ds.x * SV4; };
-#else
     auto entry_of = [&](const uint2 ds, int32_t d) -> const uint4* { return table4 + ((uint64_t)ds.x + (uint32_t)((d < 0 ? -d : d) - 1)) * SV4; };
-#endif
     if (left == 0) { if (active) T::store(m.partial, chunk, row, m.rows, T::from_gather(acc)); return; }
     if constexpr (T::GATHER_PREFETCH < 0) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -53,7 +53,15 @@ __global__ void __launch_bounds__(TB) k_tape(BpView V) {
     const uint32_t job = blockIdx.x * TB + threadIdx.x;
     if (job < V.M) step_tape(V, blockIdx.y, job);
 }
-__global__ void __launch_bounds__(TB, ZKP_LAT_WAVES) k_poly(BpView V) {
+// Register budget of the light chain kernels (k_poly, k_round_prep, k_round_sum, k_poly_sum).  In a mixed batch they start
+// beside the Groth16 gather kernels, which hold three 136-VGPR waves on every SIMD: 104 of the 512 registers are left, so a kernel
+// compiled for five waves per SIMD (<= 96 VGPRs) is resident the moment its launch is reached.  These four were at 80-106 and give
+// up 2-15 spilled registers for it.  Tried in round 3 and NOT kept: the same cap on the heavy ones (k_encode 256 -> 96 VGPRs with 211
+// spills, k_sum_t<EdMsm> 351, k_g16_cparts 478, k_g16_final 184, k_g16_witness 55): the mixed batch went from 13.7 to 14.5 ms and
+// equality alone from 4.8 to 5.5 ms -- their time is instruction latency and the scratch round trips add to it; the transcript kernels
+// cannot be capped at all (12.8 KB of LDS per 64-lane block bounds their occupancy at 3, and the compiler budgets registers for that).
+static constexpr uint32_t LAT_WAVES = 5;
+__global__ void __launch_bounds__(TB, LAT_WAVES) k_poly(BpView V) {
     ZKP_RAISE_PRIO();
     const uint32_t job = blockIdx.x * TB + threadIdx.x;
     if (job < V.M) step_poly(V, blockIdx.y, job);
@@ -75,7 +83,7 @@ __device__ __forceinline__ ScTriple triple_tree8(ScTriple t, uint32_t* lds) {
     }
     return t;
 }
-__global__ void __launch_bounds__(TW, ZKP_LAT_WAVES) k_poly_sum(BpView V) {
+__global__ void __launch_bounds__(TW, LAT_WAVES) k_poly_sum(BpView V) {
     ZKP_RAISE_PRIO();
     __shared__ uint32_t lds[24 * TW];
     const uint32_t job = blockIdx.x * 8 + (threadIdx.x & 7u), part = threadIdx.x >> 3;
@@ -90,39 +98,36 @@ __global__ void __launch_bounds__(TB) k_lr_init(BpView V) {
     const uint32_t job = blockIdx.x * TB + threadIdx.x;
     if (job < V.M) step_lr_init(V, blockIdx.y, job);
 }
-__global__ void __launch_bounds__(TB, ZKP_LAT_WAVES) k_round_prep(BpView V, uint32_t r) {
+__global__ void __launch_bounds__(TB, LAT_WAVES) k_round_prep(BpView V, uint32_t r) {
     ZKP_RAISE_PRIO();
     const uint32_t job = blockIdx.x * TB + threadIdx.x;
     if (job < V.M) step_round_prep(V, r, blockIdx.y, job);
 }
-__global__ void __launch_bounds__(TW, ZKP_LAT_WAVES) k_round_sum(BpView V, uint32_t r) {
+__global__ void __launch_bounds__(TW, LAT_WAVES) k_round_sum(BpView V, uint32_t r) {
     ZKP_RAISE_PRIO();      // <= 64 additions per lane: the 8-lane split measured slower here
     const uint32_t job = blockIdx.x * TW + threadIdx.x;
     if (job < V.M) step_round_sum(V, r, job);
 }
 // Register budget of the heavy chain kernels (transcripts, partial sums, ristretto encoding), as waves per SIMD: 1 = whatever the compiler
-// likes (k_encode: 273 registers, k_sum_t: 209).  A/B knob (-DZKP_BP_CHAIN_WAVES=3 / 4: at most 168 / 128 registers, so that a wave starts
-// in the space ONE retiring gather wave frees instead of waiting for two).  Measured in round 4 on the mixed batch: 12.26-12.37 ms
-// unconstrained, 12.26 at 3, 12.41 at 4 (range-only batches 2 % slower with either cap): no gain, left at 1.
-#ifndef ZKP_BP_CHAIN_WAVES
-#define ZKP_BP_CHAIN_WAVES 1
-#endif
+// likes (k_encode: 273 registers, k_sum_t: 209).  Tried in round 4: 3 / 4 (at most 168 / 128 registers, so that a wave starts in the space
+// ONE retiring gather wave frees instead of waiting for two).  Measured on the mixed batch: 12.26-12.37 ms unconstrained, 12.26 at 3, 12.41
+// at 4 (range-only batches 2 % slower with either cap): no gain, left at 1.
 // transcript steps: STROBE image of lane t at lds[i * TW + t] (conflict-free: consecutive lanes, consecutive banks)
-__global__ void __launch_bounds__(TW, ZKP_BP_CHAIN_WAVES) k_transcript1(BpView V) {
+__global__ void __launch_bounds__(TW, 1) k_transcript1(BpView V) {
     ZKP_RAISE_PRIO();
     __shared__ uint32_t lds[50 * TW];
     const uint32_t job = blockIdx.x * TW + threadIdx.x;
     Strobe s; s.base = lds + threadIdx.x; s.stride = TW; s.pos = 0; s.pos_begin = 0;
     if (job < V.M) step_transcript1(V, job, s);
 }
-__global__ void __launch_bounds__(TW, ZKP_BP_CHAIN_WAVES) k_transcript2(BpView V) {
+__global__ void __launch_bounds__(TW, 1) k_transcript2(BpView V) {
     ZKP_RAISE_PRIO();
     __shared__ uint32_t lds[50 * TW];
     const uint32_t job = blockIdx.x * TW + threadIdx.x;
     Strobe s; s.base = lds + threadIdx.x; s.stride = TW; s.pos = 0; s.pos_begin = 0;
     if (job < V.M) step_transcript2(V, job, s);
 }
-__global__ void __launch_bounds__(TW, ZKP_BP_CHAIN_WAVES) k_transcript_round(BpView V, uint32_t r) {
+__global__ void __launch_bounds__(TW, 1) k_transcript_round(BpView V, uint32_t r) {
     ZKP_RAISE_PRIO();
     __shared__ uint32_t lds[50 * TW];
     const uint32_t job = blockIdx.x * TW + threadIdx.x;
@@ -133,7 +138,7 @@ __global__ void __launch_bounds__(TW, ZKP_BP_CHAIN_WAVES) k_transcript_round(BpV
 // 3-level tree through LDS -- followed by k_encode (one lane per point, full waves) for the ristretto encoding.
 // (Point addition is associative and the encoding canonical, so the bytes equal reduce_encode_thread's sequential sum,
 // which the host emulation uses.)
-__global__ void __launch_bounds__(TW, ZKP_BP_CHAIN_WAVES) k_encode(ReduceView R, const uint32_t* sums) {
+__global__ void __launch_bounds__(TW, 1) k_encode(ReduceView R, const uint32_t* sums) {
     ZKP_RAISE_PRIO();
     const uint32_t row = blockIdx.x * TW + threadIdx.x, target = blockIdx.y;
     if (row >= R.rows) return;
@@ -156,7 +161,7 @@ struct EdMsm {      // edwards25519 affine-Niels tables, extended-coordinate acc
 };
 
 static constexpr uint32_t ED_SUM_ROWS = 32, ED_SUM_TB = 256;      // 8 slices per row; one wave per SIMD
-template __global__ void k_sum_t<EdMsm, ED_SUM_ROWS, ED_SUM_TB, ZKP_BP_CHAIN_WAVES>(ReduceView, uint32_t*);
+template __global__ void k_sum_t<EdMsm, ED_SUM_ROWS, ED_SUM_TB>(ReduceView, uint32_t*);
 
 // ================================================================================================ host
 namespace {
@@ -773,7 +778,7 @@ int launch_msm(const DevLayout& D, uint32_t rows, const uint32_t* digits, uint32
     return 0;
 }
 void launch_sum_ed(const ReduceView& R, uint32_t* sums, hipStream_t st) {
-    k_sum_t<EdMsm, ED_SUM_ROWS, ED_SUM_TB, ZKP_BP_CHAIN_WAVES><<<dim3((R.rows + ED_SUM_ROWS - 1) / ED_SUM_ROWS, R.ntargets), ED_SUM_TB, 0, st>>>(R, sums);
+    k_sum_t<EdMsm, ED_SUM_ROWS, ED_SUM_TB><<<dim3((R.rows + ED_SUM_ROWS - 1) / ED_SUM_ROWS, R.ntargets), ED_SUM_TB, 0, st>>>(R, sums);
 }
 int launch_reduce(const DevLayout& D, uint32_t rows, const uint32_t* partial, uint32_t* sums, uint32_t* enc, const uint64_t* out_off, uint8_t* out, hipStream_t st) {
     ReduceView R; R.rows = rows; R.ntargets = D.ntargets; R.partial = partial; R.target_chunk_begin = D.target_chunk_begin;
