@@ -41,8 +41,15 @@ enum {
 
 /* One-time setup on HIP device `device`: derives the 130 Bulletproofs generators (PedersenGens::default,
  * BulletproofGens::new party 0; replaces bp_gens_pair_bits, bulletproofs.rs:61-80), builds the
- * fixed-base window tables on the device (radix 2^16: 8.7 GB of HBM per GPU, self-checked slot against slot; the verifier uses the
- * same tables).  Idempotent.  Called implicitly (device 0) by the prove calls.
+ * fixed-base window tables on the device (self-checked slot against slot; the verifier uses the same tables, and the shards of one
+ * GPU share them).  Their radix is chosen from free HBM: 2^16 (8.7 GB) whenever it fits in half of what is free beyond an 8 GB
+ * workspace reserve, otherwise the largest of 2^15 (4.6 GB), 2^14 (2.6 GB), 2^13 (1.4 GB), 2^12 (750 MB), 2^11 (409 MB), 2^10 (222 MB)
+ * that does; proof bytes do not depend on it.  ZKP_HIP_ED_TABLE_BUDGET_MB=<MB> takes the largest radix whose table fits that budget,
+ * ZKP_HIP_ED_WBITS=10..16 forces one (any other value: ZKP_HIP_E_ARGUMENT); ZKP_HIP_E_RUNTIME ("not enough device memory for the
+ * generator tables") when not even 2^10 fits.  ZKP_HIP_ED_TABLES=lazy leaves the build (and the choice of radix) to the first call
+ * that needs the tables: a Bulletproofs prove / verify, zkp_hip_process_batch or the zkp_hip_batch_stage of a batch with a
+ * Bulletproofs op; Groth16 and STARK calls never build them.  zkp_hip_groth16_key_info(ZKP_HIP_TABLES_BP_GENERATORS, ...) reports
+ * the radix taken.  Idempotent.  Called implicitly (device 0) by the prove calls.
  * Every device initialised this way becomes one SHARD of the library (numbered in registration order). */
 int zkp_hip_init(int device);
 /* Multi-GPU (replaces the rayon fan-out of batch.rs:123-131 at node scale): registers `count` shards, shard k on
@@ -105,11 +112,15 @@ int zkp_hip_prove_consistency_batch(uint64_t n, const uint64_t* data, const uint
  * pk = ark-serialize *uncompressed* ProvingKey<Bn254> bytes, i.e. the content of the reference's
  * `{prefix}_pk.bin` key files (snark.rs:31-38,97-112).  Builds the fixed-base tables of every key point on the GPU. */
 int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len);
+#define ZKP_HIP_TABLES_BP_GENERATORS 2      /* zkp_hip_groth16_key_info: the Bulletproofs generator tables of the shard */
 /* What the loaded key of `kind` holds on the calling thread's shard: the radix of its fixed-base window tables (2^*wbits; *uneven = 1:
  * the 18-window form of radix 2^14) and the HBM they occupy (shared by the shards of one GPU).  Default policy: radix 2^13, ~27.8 GB for
  * the two circuits together; ZKP_HIP_G16_TABLE_BUDGET_MB=<MB per key> opts into larger tables (2^14-uneven, ~72 GB, measured 1.7 %
  * faster on the mixed batch), ZKP_HIP_G16_WBITS=8..15 forces a radix; a device with less free memory gets a smaller radix.  The
- * reference keeps a ProvingKey in host memory (snark.rs:40-56); this is the device-side cost of its replacement.  Any pointer may be NULL. */
+ * reference keeps a ProvingKey in host memory (snark.rs:40-56); this is the device-side cost of its replacement.  Any pointer may be NULL.
+ * kind = ZKP_HIP_TABLES_BP_GENERATORS (2): the Bulletproofs generator tables of the shard (zkp_hip_init): *wbits = 10..16, *uneven = 0,
+ * *table_bytes = 130 x windows x 2^(wbits-1) x 128 bytes; *wbits = *table_bytes = 0 (and 0 returned) while ZKP_HIP_ED_TABLES=lazy has
+ * not built them yet.  Other kinds: ZKP_HIP_E_ARGUMENT. */
 int zkp_hip_groth16_key_info(int kind, uint32_t* wbits, uint32_t* uneven, uint64_t* table_bytes);
 
 /* Circuit-specific trusted setup (replaces Groth16::circuit_specific_setup at snark.rs:318,337): toxic waste from

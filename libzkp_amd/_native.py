@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZKP_HIP_LIB") or os.path.join(_HERE, "lib", "libzkp_hip.so")      # ZKP_HIP_LIB: another build to compare against, such as the parent commit's (tools only)
 
 RANGE_PROOF_BYTES = 1478
+TABLES_BP_GENERATORS = 2          # zkp_hip_groth16_key_info kind: the Bulletproofs generator tables (include/libzkp_hip.h)
 # symbols declared in include/libzkp_hip.h (checked by tests/test_abi.py)
 EXPORTS = (
     "zkp_hip_init", "zkp_hip_shutdown", "zkp_hip_last_error", "zkp_hip_prove_range_batch",

@@ -295,6 +295,17 @@ def shutdown():
         _keys_loaded.clear()
 
 
+def generator_table_info():
+    """The Bulletproofs generator tables of the calling thread's shard (zkp_hip_groth16_key_info kind ZKP_HIP_TABLES_BP_GENERATORS):
+    {"radix": "2^w", "table_bytes": n}, or {"radix": None, "table_bytes": 0} while ZKP_HIP_ED_TABLES=lazy has not built them yet.
+    Initialises the shard (device 0) on first use, like the prove calls."""
+    L = _native.lib()
+    wbits, uneven, nbytes = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    if L.zkp_hip_groth16_key_info(_native.TABLES_BP_GENERATORS, ctypes.byref(wbits), ctypes.byref(uneven), ctypes.byref(nbytes)) != 0:
+        raise ZkpBackendError("Backend error: %s" % _native.last_error())
+    return {"radix": "2^%d" % wbits.value if wbits.value else None, "table_bytes": int(nbytes.value)}
+
+
 def export_proving_key(kind):
     """The loaded (or freshly generated) proving key of a circuit (0 equality, 1 membership) in ark-serialize form."""
     _ensure_key(kind)

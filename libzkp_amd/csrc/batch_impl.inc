@@ -296,6 +296,8 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
             default: P.n_con++; if (consistency_envelope_bytes(o.count ? o.count : 1) > P.stride_con) P.stride_con = consistency_envelope_bytes(o.count ? o.count : 1); break;
         }
     }
+    // the generator tables are built here, not at launch, when ZKP_HIP_ED_TABLES=lazy left them for the first batch that needs them
+    if ((P.n_range || P.n_thr || P.n_con) && (rc = ensure_bp())) return rc;
     // ---- layout of the staging image, the arena and the result block
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += pad256(bytes); return o; };

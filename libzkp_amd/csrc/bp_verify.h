@@ -58,8 +58,8 @@ struct VfyView {
     uint32_t* vscal;              // [17][8][M] raw scalars of the proof points
     uint32_t* partial;            // the MSM partial array; proof-point products go to chunks var_chunk0 + p
     uint32_t var_chunk0;
-    const uint32_t* table;        // generator tables (parse step: min*B, max*B): radix 2^16 in HBM (edg.h) when dig16, else the radix-1024 tables
-    uint32_t dig16 = 0;           // radix of `table` and of the fixed-base digit rows (1: the device; 0: the host emulation's small tables)
+    const uint32_t* table;        // generator tables (parse step: min*B, max*B): radix 2^wbits in HBM (edg.h) when wbits != 0, else the radix-1024 tables
+    uint32_t wbits = 0;           // radix of `table` and of the fixed-base digit rows (10..16: the device's tables; 0: the host emulation's small tables)
     // batch mode (random linear combination over the whole batch): rho = [8][M] per-job weights (Montgomery scalars), or
     // null for the per-job check.  With weights every coefficient is multiplied by rho_job; the generator coefficients then go to
     // fterm ([130][8][M] Montgomery scalars, summed over the jobs afterwards) instead of per-job digit rows.
@@ -133,15 +133,28 @@ ZKP_HD inline ge ge_scalarmult_raw(const ge& P, const sc& k) {
     return acc;
 }
 
-// v * B for a 64-bit v through the window tables of the basepoint (either radix: VfyView::dig16)
+// v * B for a 64-bit v through the window tables of the basepoint (any radix: VfyView::wbits)
 ZKP_HD inline ge vfy_mul_b_u64(const VfyView& V, uint64_t v) {
     ge acc = ge_identity();
     const sc raw = sc_words((uint32_t)v, (uint32_t)(v >> 32), 0, 0, 0, 0, 0, 0);
-    if (V.dig16) {
+    if (V.wbits == 16) {
         uint32_t d[8]; sc_recode_signed65536(d, raw);
         for (uint32_t win = 0; win < EDG_NWIN_U64; win++) {
             const int32_t a = (int32_t)(int16_t)(d[win >> 1] >> (16 * (win & 1)));
             if (a != 0) acc = edg_accumulate_from(acc, a, V.table, BASE_B, win);
+        }
+        return acc;
+    }
+    if (V.wbits != 0) {                                 // radix 2^10 .. 2^15: the signed digits of v, low window first
+        const EdgGeom g = edg_geom(V.wbits);
+        const uint32_t half = g.nent;
+        uint64_t rest = v; uint32_t carry = 0;
+        for (uint32_t win = 0; win < g.nwin_u64; win++) {
+            const uint32_t d = (uint32_t)(rest & ((1u << g.wbits) - 1u)) + carry;
+            rest >>= g.wbits;
+            carry = d > half ? 1u : 0u;
+            const int32_t a = (int32_t)d - (int32_t)(carry << g.wbits);
+            if (a != 0) acc = edg_accumulate_from(g, acc, a, V.table, BASE_B, win);
         }
         return acc;
     }
@@ -289,7 +302,7 @@ ZKP_HD inline void step_vdecode(const VfyView& V, uint32_t p, uint32_t job) {
 
 // coefficient of generator `base` for this job: per-job digits, or the weighted term of the batch check
 ZKP_HD inline void st_gen_coef(const VfyView& V, uint32_t base, uint32_t job, const sc& coef) {
-    if (V.rho == nullptr) st_digits(V.digits, base, job, V.M, coef, V.dig16);
+    if (V.rho == nullptr) st_digits(V.digits, base, job, V.M, coef, V.wbits);
     else st_sc(V.fterm, base, job, V.M, sc_mul(coef, ld_sc(V.rho, 0, job, V.M)));
 }
 // raw scalar of proof point p (weighted in batch mode)

@@ -9,9 +9,10 @@ VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy
 // 6 (consistency: no bounds; k - 1 jobs per envelope, counted on the host from each envelope's own k field)
 int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
     int rc;
+    if ((rc = ensure_bp())) return rc;
     VfyState& S = vfys();
     if (!S.ready) {
-        if ((rc = upload_set(S.set, targets_verify(EDG_NWIN)))) return rc;          // round 4: the prover's radix-2^16 tables in HBM (edg.h)
+        if ((rc = upload_set(S.set, targets_verify((uint8_t)dev().edg.nwin)))) return rc;      // round 4: the prover's tables in HBM (edg.h)
         S.ready = true;
     }
     const uint32_t jobs_per = scheme == 1 ? 2u : 1u;
@@ -67,7 +68,7 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
     VfyView V{};
     V.M = M; V.in = base + o_in; V.proof_off = (uint64_t*)(base + o_poff); V.venc_off = (uint64_t*)(base + o_voff); V.kind = base + o_kind; V.lgn = base + o_lgn;
     V.bad = (int32_t*)(base + o_bad); V.pts = (uint32_t*)(base + o_pts); V.scal = (uint32_t*)(base + o_scal); V.digits = (uint32_t*)(base + o_dig);
-    V.vscal = (uint32_t*)(base + o_vs); V.partial = (uint32_t*)(base + o_part); V.var_chunk0 = D.nchunks; V.table = dev().d_edg_table; V.dig16 = 1;
+    V.vscal = (uint32_t*)(base + o_vs); V.partial = (uint32_t*)(base + o_part); V.var_chunk0 = D.nchunks; V.table = dev().d_edg_table; V.wbits = dev().edg.wbits;
     V.job_base = (const uint32_t*)(base + o_jb); V.env_bad = (int32_t*)(base + o_eb);
     const uint32_t* d_len = (const uint32_t*)(base + o_len);
     if (scheme == 1) bpv_launch_parse(V, (uint32_t)n, stride, d_len, (const uint64_t*)(base + o_min), (const uint64_t*)(base + o_max), st);

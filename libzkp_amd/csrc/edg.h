@@ -11,6 +11,9 @@
 //
 // Entry e of (generator b, window w) = (e + 1) * 2^(16 w) * G_b as (y + x, y - x, 2 d x y), each the canonical 255-bit integer in
 // eight 32-bit words; words 24..31 of the slot are padding (one 128-byte line per gather).
+//
+// Smaller radices for devices with less free HBM (DESIGN.md "Generator tables sized to free HBM"): the geometry is a run-time EdgGeom,
+// 2^10 .. 2^16, chosen when the table is built.  The EDG_* constants and the geometry-less functions below are its radix-2^16 instance.
 #pragma once
 #include "bp_steps.h"
 
@@ -19,8 +22,22 @@ namespace zkp {
 constexpr uint32_t EDG_WBITS = 16, EDG_NWIN = 16, EDG_NENT = 1u << 15, EDG_DIGW = 8, EDG_NWIN_U64 = 5;
 constexpr uint32_t EDG_SLOT_W = 32, EDG_ENTRY_W = 24;                       // words per table slot / payload words
 constexpr uint32_t EDG_SEG = 64, EDG_NSEG = EDG_NENT / EDG_SEG, EDG_INV = 8;   // builder: 64-entry runs, one inversion per 8 entries
-ZKP_HD constexpr size_t edg_table_words() { return (size_t)NBASE * EDG_NWIN * EDG_NENT * EDG_SLOT_W; }
-ZKP_HD constexpr size_t edg_slot(uint32_t b, uint32_t w, uint32_t e) { return (((size_t)b * EDG_NWIN + w) * EDG_NENT + e) * EDG_SLOT_W; }
+
+// Table geometry at radix 2^wbits, wbits = 10..16: nwin windows cover a scalar below l < 2^253 plus the carry of the signed recoding
+// (nwin * wbits >= 254), nwin_u64 a 64-bit value plus its carry (>= 65); nent = 2^(wbits - 1) entries per window (|digit| <= nent),
+// nseg builder runs of EDG_SEG entries.  Every nwin is <= 26 = 2 * DIGW, so the digit rows keep their 13-word pitch.
+struct EdgGeom { uint32_t wbits, nwin, nwin_u64, nent, nseg; };
+constexpr uint32_t EDG_WBITS_MIN = 10, EDG_WBITS_MAX = 16;
+ZKP_HD constexpr EdgGeom edg_geom(uint32_t wbits) {
+    return EdgGeom{wbits, sc_signed_ndigits(wbits, 254), sc_signed_ndigits(wbits, 65), 1u << (wbits - 1), (1u << (wbits - 1)) / EDG_SEG};
+}
+static_assert(edg_geom(EDG_WBITS).nwin == EDG_NWIN && edg_geom(EDG_WBITS).nwin_u64 == EDG_NWIN_U64 && edg_geom(EDG_WBITS).nent == EDG_NENT &&
+              edg_geom(EDG_WBITS).nseg == EDG_NSEG, "the EDG_* constants are the radix-2^16 geometry");
+static_assert(edg_geom(EDG_WBITS_MIN).nwin <= 2 * DIGW, "digit rows hold 2 * DIGW digits");
+ZKP_HD constexpr size_t edg_table_words(const EdgGeom& g) { return (size_t)NBASE * g.nwin * g.nent * EDG_SLOT_W; }
+ZKP_HD constexpr size_t edg_slot(const EdgGeom& g, uint32_t b, uint32_t w, uint32_t e) { return (((size_t)b * g.nwin + w) * g.nent + e) * EDG_SLOT_W; }
+ZKP_HD constexpr size_t edg_table_words() { return edg_table_words(edg_geom(EDG_WBITS)); }
+ZKP_HD constexpr size_t edg_slot(uint32_t b, uint32_t w, uint32_t e) { return edg_slot(edg_geom(EDG_WBITS), b, w, e); }
 
 ZKP_HD inline ge_niels edg_unpack(const uint32_t e[EDG_ENTRY_W]) {
     ge_niels n; n.ypx = fe_fromwords(e); n.ymx = fe_fromwords(e + 8); n.xy2d = fe_fromwords(e + 16);
@@ -33,40 +50,45 @@ ZKP_HD inline ge edg_accumulate(const ge& acc, int32_t d, const uint32_t e[EDG_E
     return ge_madd(acc, n);
 }
 // reference form of one chunk (host emulation, tests): entries read straight from the table
-ZKP_HD inline ge edg_accumulate_from(const ge& acc, int32_t d, const uint32_t* table, uint32_t base, uint32_t w) {
+ZKP_HD inline ge edg_accumulate_from(const EdgGeom& g, const ge& acc, int32_t d, const uint32_t* table, uint32_t base, uint32_t w) {
     const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-    return edg_accumulate(acc, d, table + edg_slot(base, w, mag - 1));
+    return edg_accumulate(acc, d, table + edg_slot(g, base, w, mag - 1));
 }
+ZKP_HD inline ge edg_accumulate_from(const ge& acc, int32_t d, const uint32_t* table, uint32_t base, uint32_t w) { return edg_accumulate_from(edg_geom(EDG_WBITS), acc, d, table, base, w); }
 
-// ---- table construction (one-time, on the device; each function is the body of one lane).
-// 1. window bases: 2^(16 w) * G_b for w = 0..15.            lane = generator
-ZKP_HD inline void edg_step_bases(const uint32_t* gens /*[NBASE][40]*/, uint32_t* bases /*[NBASE][EDG_NWIN][40]*/, uint32_t b) {
+// ---- table construction (one-time, on the device; each function is the body of one lane).  The geometry-less forms build radix 2^16.
+// 1. window bases: 2^(wbits w) * G_b for w = 0..nwin-1.            lane = generator
+ZKP_HD inline void edg_step_bases(const EdgGeom& g, const uint32_t* gens /*[NBASE][40]*/, uint32_t* bases /*[NBASE][nwin][40]*/, uint32_t b) {
     ge p = ld_ge(gens, b, 0, 1);
-    for (uint32_t w = 0; w < EDG_NWIN; w++) {
-        st_ge(bases, b * EDG_NWIN + w, 0, 1, p);
-        for (uint32_t k = 0; k < EDG_WBITS; k++) p = ge_dbl(p);
+    for (uint32_t w = 0; w < g.nwin; w++) {
+        st_ge(bases, b * g.nwin + w, 0, 1, p);
+        for (uint32_t k = 0; k < g.wbits; k++) p = ge_dbl(p);
     }
 }
-// 2. run starts: (64 s + 1) * P for s = 0..511, P = window base.     lane = (generator, window)
-ZKP_HD inline void edg_step_starts(const uint32_t* bases, uint32_t* starts /*[NBASE * EDG_NWIN][EDG_NSEG][40]*/, uint32_t bw) {
+// 2. run starts: (64 s + 1) * P for s = 0..nseg-1, P = window base.     lane = (generator, window)
+ZKP_HD inline void edg_step_starts(const EdgGeom& g, const uint32_t* bases, uint32_t* starts /*[NBASE * nwin][nseg][40]*/, uint32_t bw) {
     const ge p = ld_ge(bases, bw, 0, 1);
     ge step = p;
     for (uint32_t k = 0; k < 6; k++) step = ge_dbl(step);                 // 64 P
     ge acc = p;
-    for (uint32_t s = 0; s < EDG_NSEG; s++) { st_ge(starts, (size_t)bw * EDG_NSEG + s, 0, 1, acc); acc = ge_add(acc, step); }
+    for (uint32_t s = 0; s < g.nseg; s++) { st_ge(starts, (size_t)bw * g.nseg + s, 0, 1, acc); acc = ge_add(acc, step); }
 }
 // 3. a run of 64 consecutive multiples, left in their slots as projective (X, Y, Z) limbs.     lane = (generator, window, run)
-ZKP_HD inline void edg_step_fill(const uint32_t* bases, const uint32_t* starts, uint32_t* table, uint32_t bw, uint32_t s) {
+ZKP_HD inline void edg_step_fill(const EdgGeom& g, const uint32_t* bases, const uint32_t* starts, uint32_t* table, uint32_t bw, uint32_t s) {
     const ge p = ld_ge(bases, bw, 0, 1);
-    ge acc = ld_ge(starts, (size_t)bw * EDG_NSEG + s, 0, 1);
-    uint32_t* q = table + ((size_t)bw * EDG_NENT + (size_t)s * EDG_SEG) * EDG_SLOT_W;
+    ge acc = ld_ge(starts, (size_t)bw * g.nseg + s, 0, 1);
+    uint32_t* q = table + ((size_t)bw * g.nent + (size_t)s * EDG_SEG) * EDG_SLOT_W;
     for (uint32_t e = 0; e < EDG_SEG; e++) {
         ZKP_UNROLL for (int k = 0; k < 10; k++) { q[k] = acc.X.v[k]; q[10 + k] = acc.Y.v[k]; q[20 + k] = acc.Z.v[k]; }
         q += EDG_SLOT_W;
         acc = ge_add(acc, p);
     }
 }
+ZKP_HD inline void edg_step_bases(const uint32_t* gens, uint32_t* bases, uint32_t b) { edg_step_bases(edg_geom(EDG_WBITS), gens, bases, b); }
+ZKP_HD inline void edg_step_starts(const uint32_t* bases, uint32_t* starts, uint32_t bw) { edg_step_starts(edg_geom(EDG_WBITS), bases, starts, bw); }
+ZKP_HD inline void edg_step_fill(const uint32_t* bases, const uint32_t* starts, uint32_t* table, uint32_t bw, uint32_t s) { edg_step_fill(edg_geom(EDG_WBITS), bases, starts, table, bw, s); }
 // 4. eight slots from projective to packed affine Niels with ONE field inversion (Montgomery's trick).     lane = 8 consecutive slots
+// (every geometry: nent is a multiple of EDG_INV, so a group never straddles two windows)
 ZKP_HD inline fe edg_fe_invert(const fe& z) {              // z^(p-2) = (z^(2^252-3))^8 * z^3
     fe t = fe_pow22523(z);
     t = fe_sq(fe_sq(fe_sq(t)));
@@ -94,8 +116,8 @@ ZKP_HD inline void edg_step_affine(uint32_t* table, size_t group) {
         ZKP_UNROLL for (int k = EDG_ENTRY_W; k < (int)EDG_SLOT_W; k++) q[k] = 0;
     }
 }
-// 5. self-check of the finished table, all of it: entry[e] + entry[0] == entry[e + 1] inside a window, 2 * entry[32767] of window w ==
-// entry[0] of window w + 1, and entry[0] of window 0 == the generator.  By induction every slot then holds the multiple it stands for.
+// 5. self-check of the finished table, all of it: entry[e] + entry[0] == entry[e + 1] inside a window, 2 * entry[nent - 1]
+// of window w == entry[0] of window w + 1 (2^wbits * the window base), and entry[0] of window 0 == the generator.  By induction every slot then holds the multiple it stands for.
 // lane = (generator, window, e); returns false on a mismatch
 ZKP_HD inline bool edg_niels_equals(const ge& p, const uint32_t e[EDG_ENTRY_W]) {       // projective p against an affine entry
     const ge_niels n = edg_unpack(e);
@@ -109,16 +131,17 @@ ZKP_HD inline ge edg_point_of(const uint32_t e[EDG_ENTRY_W]) {                  
     p.T = fe_mul(p.X, p.Y); p.X = fe_carry(fe_add(p.X, p.X)); p.Y = fe_carry(fe_add(p.Y, p.Y)); p.Z.v[0] = 4;
     return p;
 }
-ZKP_HD inline bool edg_step_check(const uint32_t* table, const uint32_t* gens, uint32_t b, uint32_t w, uint32_t e) {
-    const uint32_t* cur = table + edg_slot(b, w, e);
-    if (e + 1 < EDG_NENT) {
-        const ge sum = ge_madd(edg_point_of(cur), edg_unpack(table + edg_slot(b, w, 0)));
+ZKP_HD inline bool edg_step_check(const EdgGeom& g, const uint32_t* table, const uint32_t* gens, uint32_t b, uint32_t w, uint32_t e) {
+    const uint32_t* cur = table + edg_slot(g, b, w, e);
+    if (e + 1 < g.nent) {
+        const ge sum = ge_madd(edg_point_of(cur), edg_unpack(table + edg_slot(g, b, w, 0)));
         if (!edg_niels_equals(sum, cur + EDG_SLOT_W)) return false;
-    } else if (w + 1 < EDG_NWIN) {
-        if (!edg_niels_equals(ge_dbl(edg_point_of(cur)), table + edg_slot(b, w + 1, 0))) return false;
+    } else if (w + 1 < g.nwin) {
+        if (!edg_niels_equals(ge_dbl(edg_point_of(cur)), table + edg_slot(g, b, w + 1, 0))) return false;
     }
     if (w == 0 && e == 0 && !edg_niels_equals(ld_ge(gens, b, 0, 1), cur)) return false;
     return true;
 }
+ZKP_HD inline bool edg_step_check(const uint32_t* table, const uint32_t* gens, uint32_t b, uint32_t w, uint32_t e) { return edg_step_check(edg_geom(EDG_WBITS), table, gens, b, w, e); }
 
 }  // namespace zkp

@@ -1,4 +1,4 @@
-// ed25519 fixed-base MSM over HBM-resident radix-2^16 tables (edg.h) and the kernels that build those tables: a translation unit of
+// ed25519 fixed-base MSM over HBM-resident radix-2^10 .. 2^16 tables (edg.h) and the kernels that build those tables: a translation unit of
 // its own so that the Bulletproofs host code and the Groth16 kernels need not recompile with it.
 #include "edg_launch.h"
 #include "msm_kernel.h"
@@ -41,37 +41,54 @@ void edg_launch_msm(const MsmView& m, uint32_t ngroups, uint32_t nblocks, hipStr
     else k_msm_gather<EdGather><<<grid, 256, gather_lds_bytes<EdGather>(), st>>>(m, ngroups, nblocks);
 }
 
-// ---- table construction (edg.h: steps 1-5)
-__global__ void __launch_bounds__(64) k_edg_bases(const uint32_t* gens, uint32_t* bases) {
+// ---- table construction (edg.h: steps 1-5), one instantiation per radix: the geometry is a compile-time constant inside each kernel, so
+// the radix-2^16 kernels are the code they were before the other radices existed (a run-time geometry cost them 2-6 registers)
+template <uint32_t WB> __global__ void __launch_bounds__(64) k_edg_bases(const uint32_t* gens, uint32_t* bases) {
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
-    if (b < NBASE) edg_step_bases(gens, bases, b);
+    if (b < NBASE) edg_step_bases(edg_geom(WB), gens, bases, b);
 }
-__global__ void __launch_bounds__(64) k_edg_starts(const uint32_t* bases, uint32_t* starts) {
+template <uint32_t WB> __global__ void __launch_bounds__(64) k_edg_starts(const uint32_t* bases, uint32_t* starts) {
+    constexpr EdgGeom g = edg_geom(WB);
     const uint32_t bw = blockIdx.x * 64 + threadIdx.x;
-    if (bw < NBASE * EDG_NWIN) edg_step_starts(bases, starts, bw);
+    if (bw < NBASE * g.nwin) edg_step_starts(g, bases, starts, bw);
 }
-__global__ void __launch_bounds__(256) k_edg_fill(const uint32_t* bases, const uint32_t* starts, uint32_t* table) {
+template <uint32_t WB> __global__ void __launch_bounds__(256) k_edg_fill(const uint32_t* bases, const uint32_t* starts, uint32_t* table) {
+    constexpr EdgGeom g = edg_geom(WB);
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;                 // (bw, run), run fastest
-    if (t < NBASE * EDG_NWIN * EDG_NSEG) edg_step_fill(bases, starts, table, t / EDG_NSEG, t % EDG_NSEG);
+    if (t < NBASE * g.nwin * g.nseg) edg_step_fill(g, bases, starts, table, t / g.nseg, t % g.nseg);
 }
-__global__ void __launch_bounds__(256) k_edg_affine(uint32_t* table) {
-    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g < (size_t)NBASE * EDG_NWIN * EDG_NENT / EDG_INV) edg_step_affine(table, g);
+template <uint32_t WB> __global__ void __launch_bounds__(256) k_edg_affine(uint32_t* table) {
+    constexpr EdgGeom g = edg_geom(WB);
+    const size_t grp = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (grp < (size_t)NBASE * g.nwin * g.nent / EDG_INV) edg_step_affine(table, grp);
 }
-__global__ void __launch_bounds__(256) k_edg_check(const uint32_t* table, const uint32_t* gens, int* bad) {
+template <uint32_t WB> __global__ void __launch_bounds__(256) k_edg_check(const uint32_t* table, const uint32_t* gens, int* bad) {
+    constexpr EdgGeom g = edg_geom(WB);
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (size_t)NBASE * EDG_NWIN * EDG_NENT) return;
-    const uint32_t e = (uint32_t)(t % EDG_NENT), bw = (uint32_t)(t / EDG_NENT);
-    if (!edg_step_check(table, gens, bw / EDG_NWIN, bw % EDG_NWIN, e)) atomicAdd(bad, 1);
+    if (t >= (size_t)NBASE * g.nwin * g.nent) return;
+    const uint32_t e = (uint32_t)(t % g.nent), bw = (uint32_t)(t / g.nent);
+    if (!edg_step_check(g, table, gens, bw / g.nwin, bw % g.nwin, e)) atomicAdd(bad, 1);
 }
-size_t edg_build_scratch_words() { return (size_t)NBASE * EDG_NWIN * (EDG_NSEG + 1) * GE_W; }
-void edg_launch_build(const uint32_t* d_gens, uint32_t* d_table, uint32_t* d_scratch, int* d_bad, hipStream_t st) {
-    uint32_t* bases = d_scratch;                                        // [NBASE * EDG_NWIN][40]
-    uint32_t* starts = d_scratch + (size_t)NBASE * EDG_NWIN * GE_W;     // [NBASE * EDG_NWIN][EDG_NSEG][40]
-    k_edg_bases<<<(NBASE + 63) / 64, 64, 0, st>>>(d_gens, bases);
-    k_edg_starts<<<(NBASE * EDG_NWIN + 63) / 64, 64, 0, st>>>(bases, starts);
-    k_edg_fill<<<(NBASE * EDG_NWIN * EDG_NSEG + 255) / 256, 256, 0, st>>>(bases, starts, d_table);
-    const size_t groups = (size_t)NBASE * EDG_NWIN * EDG_NENT / EDG_INV, slots = (size_t)NBASE * EDG_NWIN * EDG_NENT;
-    k_edg_affine<<<(uint32_t)((groups + 255) / 256), 256, 0, st>>>(d_table);
-    k_edg_check<<<(uint32_t)((slots + 255) / 256), 256, 0, st>>>(d_table, d_gens, d_bad);
+template <uint32_t WB> void edg_launch_build_at(const uint32_t* d_gens, uint32_t* d_table, uint32_t* d_scratch, int* d_bad, hipStream_t st) {
+    constexpr EdgGeom g = edg_geom(WB);
+    uint32_t* bases = d_scratch;                                        // [NBASE * nwin][40]
+    uint32_t* starts = d_scratch + (size_t)NBASE * g.nwin * GE_W;       // [NBASE * nwin][nseg][40]
+    k_edg_bases<WB><<<(NBASE + 63) / 64, 64, 0, st>>>(d_gens, bases);
+    k_edg_starts<WB><<<(NBASE * g.nwin + 63) / 64, 64, 0, st>>>(bases, starts);
+    k_edg_fill<WB><<<(NBASE * g.nwin * g.nseg + 255) / 256, 256, 0, st>>>(bases, starts, d_table);
+    const size_t groups = (size_t)NBASE * g.nwin * g.nent / EDG_INV, slots = (size_t)NBASE * g.nwin * g.nent;
+    k_edg_affine<WB><<<(uint32_t)((groups + 255) / 256), 256, 0, st>>>(d_table);
+    k_edg_check<WB><<<(uint32_t)((slots + 255) / 256), 256, 0, st>>>(d_table, d_gens, d_bad);
+}
+size_t edg_build_scratch_words(const EdgGeom& g) { return (size_t)NBASE * g.nwin * (g.nseg + 1) * GE_W; }
+void edg_launch_build(const EdgGeom& g, const uint32_t* d_gens, uint32_t* d_table, uint32_t* d_scratch, int* d_bad, hipStream_t st) {
+    switch (g.wbits) {
+        case 10: edg_launch_build_at<10>(d_gens, d_table, d_scratch, d_bad, st); break;
+        case 11: edg_launch_build_at<11>(d_gens, d_table, d_scratch, d_bad, st); break;
+        case 12: edg_launch_build_at<12>(d_gens, d_table, d_scratch, d_bad, st); break;
+        case 13: edg_launch_build_at<13>(d_gens, d_table, d_scratch, d_bad, st); break;
+        case 14: edg_launch_build_at<14>(d_gens, d_table, d_scratch, d_bad, st); break;
+        case 15: edg_launch_build_at<15>(d_gens, d_table, d_scratch, d_bad, st); break;
+        default: edg_launch_build_at<16>(d_gens, d_table, d_scratch, d_bad, st); break;
+    }
 }

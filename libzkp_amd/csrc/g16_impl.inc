@@ -805,9 +805,16 @@ int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len) try {
 } ZKP_API_CATCH_INT
 
 int zkp_hip_groth16_key_info(int kind, uint32_t* wbits, uint32_t* uneven, uint64_t* table_bytes) try {
-    if (kind != G16_EQUALITY && kind != G16_MEMBERSHIP) return fail(ZKP_HIP_E_ARGUMENT, "unknown circuit kind");
+    if (kind != G16_EQUALITY && kind != G16_MEMBERSHIP && kind != ZKP_HIP_TABLES_BP_GENERATORS) return fail(ZKP_HIP_E_ARGUMENT, "unknown circuit kind");
     Bind bind; int rc = bind.open();
     if (rc) return rc;
+    if (kind == ZKP_HIP_TABLES_BP_GENERATORS) {          // the shard's Bulletproofs generator tables (zeros while ZKP_HIP_ED_TABLES=lazy has not built them)
+        const EdgGeom& g = dev().edg;
+        if (wbits) *wbits = g.wbits;
+        if (uneven) *uneven = 0;
+        if (table_bytes) *table_bytes = dev().d_edg_table ? (uint64_t)edg_table_words(g) * 4 : 0;
+        return 0;
+    }
     const G16Key& K = g16s().key[kind];
     if (!K.loaded) return fail(ZKP_HIP_E_ARGUMENT, "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
     if (wbits) *wbits = K.rx.wbits;

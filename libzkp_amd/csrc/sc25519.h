@@ -237,6 +237,10 @@ ZKP_HD inline void sc_recode_signed65536(uint32_t packed[8], const sc& raw) {
     }
 }
 
+// digits of a signed radix-2^wb recoding of a value of `bits` bits: the smallest count whose wb * count covers the bits plus the
+// carry out of the top digit (bits = 254 for a scalar below l < 2^253, 65 for a 64-bit value)
+ZKP_HD constexpr uint32_t sc_signed_ndigits(uint32_t wb, uint32_t bits) { return (bits + wb - 1) / wb; }
+
 // signed radix-2^WB recoding of a canonical raw scalar: ND digits in [-(2^(WB-1) - 1), 2^(WB-1)], two 16-bit digits per word
 // (WB <= 15; WB * ND must cover the scalar's bit length plus the carry).  WB = 10, ND = 26 is sc_recode_signed1024.
 template <int WB, int ND> ZKP_HD inline void sc_recode_signed(uint32_t* packed, const sc& raw) {
@@ -250,6 +254,28 @@ template <int WB, int ND> ZKP_HD inline void sc_recode_signed(uint32_t* packed, 
         d = (d - (carry << WB)) & 0xffffu;
         if ((j & 1) == 0) packed[j >> 1] = d; else packed[j >> 1] |= d << 16;
     }
+}
+// The same recoding with the radix a run-time value (wb = 11..15, nd digits): no array is indexed at run time, so nothing goes to
+// scratch -- the scalar's words are picked with selects, and each packed word is stored to q[k * stride] as soon as it is complete.
+ZKP_HD inline uint32_t sc_word_or_zero(const sc& raw, uint32_t i) {
+    uint32_t x = 0;
+    ZKP_UNROLL for (uint32_t k = 0; k < 8; k++) x = i == k ? raw.v[k] : x;
+    return x;
+}
+ZKP_HD inline void sc_recode_signed_rt(uint32_t* q, size_t stride, const sc& raw, uint32_t wb, uint32_t nd) {
+    const uint32_t mask = (1u << wb) - 1u, half = 1u << (wb - 1);
+    uint32_t carry = 0, pk = 0;
+    for (uint32_t j = 0; j < nd; j++) {
+        const uint32_t bit = wb * j, wd = bit >> 5, sh = bit & 31u;
+        uint32_t x = sc_word_or_zero(raw, wd) >> sh;
+        if (sh + wb > 32u) x |= sc_word_or_zero(raw, wd + 1) << (32u - sh);
+        uint32_t d = (x & mask) + carry;                            // 0 .. 2^wb
+        carry = d > half ? 1u : 0u;                                 // digit = d - 2^wb * carry in [-(2^(wb-1) - 1), 2^(wb-1)]
+        d = (d - (carry << wb)) & 0xffffu;
+        if ((j & 1u) == 0) pk = d;
+        else { q[(size_t)(j >> 1) * stride] = pk | (d << 16); }
+    }
+    if (nd & 1u) q[(size_t)(nd >> 1) * stride] = pk;
 }
 
 }  // namespace zkp

@@ -308,7 +308,9 @@ struct Device {
     int num_cu = 256;
     int msm_prio_now = 0;               // set by the mixed-batch scheduler while it enqueues the Bulletproofs chain of a batch that also holds Groth16 work: the ed25519 MSM waves raise their issue priority
     hipStream_t stream = nullptr;
-    uint32_t* d_edg_table = nullptr;    // radix-2^16 tables, gathered per lane from HBM (edg.h: every MSM of the prover)
+    uint32_t* d_edg_table = nullptr;    // the generator tables, gathered per lane from HBM (edg.h: every ed25519 MSM of the library)
+    EdgGeom edg = {0, 0, 0, 0, 0};      // their geometry (radix 2^edg.wbits, chosen when they are built; wbits = 0: no tables yet)
+    bool bp_ready = false;              // the tables and the launch sets built from their geometry exist (ensure_bp)
     int edg_blocks_per_cu = 3;
     // MSM chunkings: phase 1 and the inner-product rounds depend on the proofs' bit width n = 8 << w (w = 0..3); the
     // 64-bit family is built at init, narrower ones on first use
@@ -509,7 +511,8 @@ int upload_set(LayoutSet& S, const std::vector<SlotList>& targets) {
     uint32_t total = 0; for (auto& t : targets) for (auto& sl : t) total += sl.second;
     auto push = [&](const MsmLayout& L) -> int {
         S.cand.emplace_back();
-        const GatherShape edg_shape{EDG_NENT, EDG_NWIN * EDG_NENT, 0u, DIGW};      // (digit rows keep their 13-word pitch)
+        const EdgGeom& g = dev().edg;
+        const GatherShape edg_shape{g.nent, g.nwin * g.nent, 0u, DIGW};      // (digit rows keep their 13-word pitch)
         int rc = upload_layout(S.cand.back(), L, &edg_shape); if (rc) return rc;
         if (S.cand.back().nchunks > S.max_chunks) S.max_chunks = S.cand.back().nchunks;
         return 0;
@@ -553,9 +556,11 @@ const DevLayout& pick_layout(const LayoutSet& S, uint32_t rows) {
 int ensure_family(uint32_t lg) {
     Device::Family& F = dev().fam[lg - 3];
     if (F.ready) return 0;
+    if (!dev().d_edg_table) return fail(ZKP_HIP_E_RUNTIME, "the generator tables have not been built on this shard");
+    const EdgGeom& g = dev().edg;
     int rc;
-    if ((rc = upload_set(F.p1, targets_phase1(1u << lg, EDG_NWIN, EDG_NWIN_U64)))) return rc;
-    for (uint32_t r = 0; r < lg; r++) if ((rc = upload_set(F.rd[r], targets_round(r, 1u << lg, EDG_NWIN)))) return rc;
+    if ((rc = upload_set(F.p1, targets_phase1(1u << lg, (uint8_t)g.nwin, (uint8_t)g.nwin_u64)))) return rc;
+    for (uint32_t r = 0; r < lg; r++) if ((rc = upload_set(F.rd[r], targets_round(r, 1u << lg, (uint8_t)g.nwin)))) return rc;
     if (F.p1.max_chunks > dev().max_chunks) dev().max_chunks = F.p1.max_chunks;
     for (uint32_t r = 0; r < lg; r++) if (F.rd[r].max_chunks > dev().max_chunks) dev().max_chunks = F.rd[r].max_chunks;
     F.ready = true;
@@ -566,11 +571,12 @@ bool bits_to_lg(uint32_t n_bits, uint32_t* lg) {     // RangeProof::prove_single
     return false;
 }
 
-// The prover's tables (edg.h): 130 generators x 16 windows x 32 768 affine-Niels entries in 128-byte slots = 8.7 GB of HBM, computed on the
-// device from the 130 generators (the host derives only those: RFC 9496 one-way map, bp_layout.h) and checked slot against slot before the
-// shard is declared ready.  Takes ~0.1 s.
-// One table per physical GPU in the process: shards registered on the same HIP device share it (like the Groth16 key tables).
-struct EdgTables { std::mutex mu; struct E { int hip_dev; uint32_t* table; int refs; }; std::vector<E> v; };
+// The prover's tables (edg.h): 130 generators x 16 windows x 32 768 affine-Niels entries in 128-byte slots = 8.7 GB of HBM at radix 2^16,
+// computed on the device from the 130 generators (the host derives only those: RFC 9496 one-way map, bp_layout.h) and checked slot against
+// slot before they are used.  Takes ~0.1 s.  Smaller radices for a device with less free memory (choose_ed_radix).
+// One table per physical GPU in the process: shards registered on the same HIP device share it (like the Groth16 key tables), and a
+// shard that finds one takes its geometry too.
+struct EdgTables { std::mutex mu; struct E { int hip_dev; uint32_t* table; int refs; EdgGeom geom; }; std::vector<E> v; };
 EdgTables& edg_tables() { static EdgTables* r = new EdgTables(); return *r; }
 void release_edg_table() {
     Device& D = dev();
@@ -578,7 +584,44 @@ void release_edg_table() {
     EdgTables& R = edg_tables();
     std::lock_guard<std::mutex> lk(R.mu);
     for (auto& e : R.v) if (e.table == D.d_edg_table && e.refs > 0 && --e.refs == 0) { (void)hipFree(e.table); e.table = nullptr; }
-    D.d_edg_table = nullptr;
+    D.d_edg_table = nullptr; D.edg = EdgGeom{0, 0, 0, 0, 0};
+}
+uint64_t edg_table_bytes(uint32_t wbits) { return (uint64_t)edg_table_words(edg_geom(wbits)) * 4; }
+uint64_t edg_scratch_bytes(uint32_t wbits) { return (uint64_t)edg_build_scratch_words(edg_geom(wbits)) * 4; }
+// The radix of the generator tables, chosen when they are built.  DEFAULT: 2^16 whenever it fits, so that a device with room behaves as
+// it always has; otherwise the largest radix 2^15 .. 2^10 that fits.  "Fits": table + build scratch <= half of what the device has free
+// beyond the 8 GB workspace reserve of the Groth16 rule (choose_radix, g16_impl.inc).  The other half is left for the Groth16 key tables,
+// which are loaded later and size themselves from what is free then (45 % per key beyond the same reserve); an idle MI355X has ~280 GB
+// free and gets radix 2^16.  Opt-ins: ZKP_HIP_ED_TABLE_BUDGET_MB=<MB> takes the largest radix whose table fits that budget instead;
+// ZKP_HIP_ED_WBITS=10..16 forces one.
+int choose_ed_radix(uint32_t* wbits_out) {
+    const char* forced = getenv("ZKP_HIP_ED_WBITS");
+    if (forced && *forced) {
+        char* end = nullptr;
+        const long w = strtol(forced, &end, 10);
+        if (*end != 0 || w < (long)EDG_WBITS_MIN || w > (long)EDG_WBITS_MAX) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_ED_WBITS must be 10..16");
+        *wbits_out = (uint32_t)w; return 0;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const int budget_mb = env_int("ZKP_HIP_ED_TABLE_BUDGET_MB", 0);
+    const uint64_t reserve = 8ull << 30;
+    const uint64_t fits = free_b > reserve ? (uint64_t)(free_b - reserve) / 2 : 0;
+    const uint64_t budget = budget_mb > 0 ? (uint64_t)budget_mb << 20 : fits;
+    for (uint32_t w = EDG_WBITS_MAX; w >= EDG_WBITS_MIN; w--)
+        if (edg_table_bytes(w) + (budget_mb > 0 ? 0 : edg_scratch_bytes(w)) <= budget) { *wbits_out = w; return 0; }
+    char msg[256];
+    snprintf(msg, sizeof msg, "not enough device memory for the generator tables: %llu MB at the smallest radix (2^%u), budget %llu MB (%llu MB free)",
+             (unsigned long long)(edg_table_bytes(EDG_WBITS_MIN) >> 20), EDG_WBITS_MIN, (unsigned long long)(budget >> 20), (unsigned long long)(free_b >> 20));
+    return fail(ZKP_HIP_E_RUNTIME, msg);
+}
+// ZKP_HIP_ED_TABLES=lazy: the tables are built by the first call that needs them (ensure_bp) instead of by the shard's initialisation
+int ed_tables_lazy(bool* lazy) {
+    const char* v = getenv("ZKP_HIP_ED_TABLES");
+    *lazy = false;
+    if (!v || !*v || !strcmp(v, "eager")) return 0;
+    if (!strcmp(v, "lazy")) { *lazy = true; return 0; }
+    return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_ED_TABLES must be eager or lazy");
 }
 int build_edg_table() {
     Device& D = dev();
@@ -589,15 +632,19 @@ int build_edg_table() {
         const uint32_t occ = edg_msm_blocks_per_cu();
         D.edg_blocks_per_cu = occ ? (int)occ : 3;
     }
-    for (auto& e : R.v) if (e.hip_dev == D.hip_dev && e.refs > 0) { e.refs++; D.d_edg_table = e.table; return 0; }
+    for (auto& e : R.v) if (e.hip_dev == D.hip_dev && e.refs > 0) { e.refs++; D.d_edg_table = e.table; D.edg = e.geom; return 0; }
+    uint32_t wbits = 0;
+    int rc = choose_ed_radix(&wbits);
+    if (rc) return rc;
+    const EdgGeom g = edg_geom(wbits);
     ge gens[NBASE]; host_generators(gens);
     std::vector<uint32_t> gw((size_t)NBASE * GE_W);
     for (uint32_t b = 0; b < NBASE; b++) st_ge(gw.data(), b, 0, 1, gens[b]);
     uint32_t *d_gens = nullptr, *d_scratch = nullptr; int* d_bad = nullptr;
-    const size_t table_bytes = edg_table_words() * 4, scratch_bytes = edg_build_scratch_words() * 4;
+    const size_t table_bytes = edg_table_words(g) * 4, scratch_bytes = edg_build_scratch_words(g) * 4;
     if (hipMalloc(&D.d_edg_table, table_bytes) != hipSuccess) {
         (void)hipGetLastError(); D.d_edg_table = nullptr;
-        char msg[200]; snprintf(msg, sizeof msg, "out of device memory allocating the %llu MB of generator window tables", (unsigned long long)(table_bytes >> 20));
+        char msg[200]; snprintf(msg, sizeof msg, "out of device memory allocating the %llu MB of generator window tables (radix 2^%u)", (unsigned long long)(table_bytes >> 20), wbits);
         return fail(ZKP_HIP_E_RUNTIME, msg);
     }
     auto drop = [&]() { (void)hipFree(d_gens); (void)hipFree(d_scratch); (void)hipFree(d_bad); };
@@ -608,7 +655,7 @@ int build_edg_table() {
     if (e == hipSuccess) e = hipMemcpyAsync(d_gens, gw.data(), gw.size() * 4, hipMemcpyHostToDevice, D.stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int), D.stream);
     if (e != hipSuccess) return give_up(ZKP_HIP_E_RUNTIME, std::string("generator tables: ") + hipGetErrorString(e));
-    edg_launch_build(d_gens, D.d_edg_table, d_scratch, d_bad, D.stream);
+    edg_launch_build(g, d_gens, D.d_edg_table, d_scratch, d_bad, D.stream);
     int bad = -1;
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, D.stream);
@@ -616,7 +663,24 @@ int build_edg_table() {
     if (e != hipSuccess) return give_up(ZKP_HIP_E_RUNTIME, std::string("generator tables: ") + hipGetErrorString(e));
     if (bad != 0) { char msg[160]; snprintf(msg, sizeof msg, "generator window tables failed their self-check (%d inconsistent slots)", bad); return give_up(ZKP_HIP_E_RUNTIME, msg); }
     drop();
-    R.v.push_back({D.hip_dev, D.d_edg_table, 1});
+    D.edg = g;
+    R.v.push_back({D.hip_dev, D.d_edg_table, 1, g});
+    return 0;
+}
+// The generator tables and every launch set whose shape follows their geometry (caller holds the shard's mutex).  At initialisation by
+// default; with ZKP_HIP_ED_TABLES=lazy at the first call that needs them (prove / verify of the Bulletproofs framings, the staging of a
+// batch that holds one), never for a Groth16 or STARK call.
+int ensure_bp() {
+    Device& D = dev();
+    if (D.bp_ready) return 0;
+    int rc;
+    if ((rc = build_edg_table())) return rc;
+    D.max_chunks = 0;
+    if ((rc = upload_set(D.p2, targets_phase2((uint8_t)D.edg.nwin)))) return rc;
+    if ((rc = upload_set(D.ct, targets_ctask((uint8_t)D.edg.nwin, (uint8_t)D.edg.nwin_u64)))) return rc;
+    D.max_chunks = D.p2.max_chunks;
+    if ((rc = ensure_family(6))) return rc;
+    D.bp_ready = true;
     return 0;
 }
 
@@ -624,16 +688,13 @@ int build_edg_table() {
 int init_device() {
     Device& D = dev();
     if (D.ready) return 0;
+    bool lazy = false;
+    int rc = ed_tables_lazy(&lazy);
+    if (rc) return rc;
     hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, D.hip_dev));
     D.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY(hipStreamCreateWithFlags(&D.stream, hipStreamNonBlocking));
-    int rc;
-    if ((rc = build_edg_table())) return rc;
-    D.max_chunks = 0;
-    if ((rc = upload_set(D.p2, targets_phase2(EDG_NWIN)))) return rc;
-    if ((rc = upload_set(D.ct, targets_ctask(EDG_NWIN, EDG_NWIN_U64)))) return rc;
-    D.max_chunks = D.p2.max_chunks;
-    if ((rc = ensure_family(6))) return rc;
+    if (!D.stream) HIP_TRY(hipStreamCreateWithFlags(&D.stream, hipStreamNonBlocking));
+    if (!lazy && (rc = ensure_bp())) return rc;
     D.ready = true;
     return 0;
 }
@@ -731,7 +792,7 @@ size_t carve(uint8_t* base, uint32_t M, uint32_t C, uint32_t max_chunks, Ws* w) 
     t.J.bl_plus = (int32_t*)take(4ull * M); t.J.bl_minus = (int32_t*)take(4ull * M); t.J.kind = (uint8_t*)take(M);
     t.J.proof_off = (uint64_t*)take(8ull * M); t.J.commit_off = (uint64_t*)take(8ull * M);
     t.J.ct_v = (uint64_t*)take(8ull * C); t.J.ct_seed_ix = (uint32_t*)take(4ull * C); t.J.ct_bl_ix = (uint32_t*)take(4ull * C); t.J.ct_off = (uint64_t*)take(8ull * C);
-    t.V.dig16 = 1; t.T.dig16 = 1;             // the device prover's MSMs walk the radix-2^16 tables (edg.h)
+    t.V.wbits = dev().edg.wbits; t.T.wbits = dev().edg.wbits;      // the device prover's MSMs walk the shard's tables (edg.h)
     t.V.M = M; t.V.v = t.J.v; t.V.seed_ix = t.J.seed_ix; t.V.proof_ix = t.J.proof_ix; t.V.bl_plus = t.J.bl_plus; t.V.bl_minus = t.J.bl_minus;
     t.V.kind = t.J.kind; t.V.proof_off = t.J.proof_off; t.V.commit_off = t.J.commit_off;
     t.V.tape = (uint32_t*)take(W * TAPE_SLOTS); t.V.gamma = (uint32_t*)take(W);
@@ -769,7 +830,8 @@ int launch_msm(const DevLayout& D, uint32_t rows, const uint32_t* digits, uint32
     int rc = prof_begin(dev().prof[0], st, &e1);
     if (rc) return rc;
     {
-        m.nwin = EDG_NWIN; m.nent = EDG_NENT; m.digw = DIGW; m.slot_ent = EDG_NWIN * EDG_NENT; m.uneven = 0;
+        const EdgGeom& g = dev().edg;
+        m.nwin = g.nwin; m.nent = g.nent; m.digw = DIGW; m.slot_ent = g.nwin * g.nent; m.uneven = 0;
         m.steps = D.steps; m.chunk_step0 = D.chunk_step0;
         const uint32_t tb = edg_msm_rows_per_block(), ngroups = (rows + tb - 1) / tb, nblocks = D.nchunks * ngroups;
         ZKP_TRACED("k_msm_gather<EdGather>", st, edg_launch_msm(m, ngroups, nblocks, st, dev().msm_prio_now != 0));
@@ -919,6 +981,8 @@ int run_jobs_on(SubBatch& sb, const HostJobs& H, const uint8_t* d_seeds, uint8_t
 
 // out: host buffer already holding every framing byte; proofs and commitments are filled in by the device
 int run_host_jobs(const HostJobs& H, const uint8_t* seeds, size_t nseeds, uint8_t* out, size_t out_bytes, uint32_t lg = 6) {
+    int rc = ensure_bp();
+    if (rc) return rc;
     if (H.v.empty() && H.ct_v.empty()) return 0;
     hipStream_t st = dev().stream;
     DevScope mem;
@@ -926,7 +990,7 @@ int run_host_jobs(const HostJobs& H, const uint8_t* seeds, size_t nseeds, uint8_
     HIP_TRY(mem.alloc(&d_seeds, 32 * nseeds)); HIP_TRY(mem.alloc(&d_out, out_bytes));
     HIP_TRY(hipMemcpyAsync(d_seeds, seeds, 32 * nseeds, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, st));
-    int rc = run_jobs_on(dev().sub[0], H, d_seeds, d_out, lg, st);
+    rc = run_jobs_on(dev().sub[0], H, d_seeds, d_out, lg, st);
     if (rc == 0) HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));          // nothing may still be using the per-call buffers when `mem` goes
     return rc;
@@ -1104,7 +1168,7 @@ void zkp_hip_shutdown(void) try {
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
-        d->ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
+        d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
     }
 } ZKP_API_CATCH_VOID
@@ -1147,7 +1211,7 @@ int zkp_hip_prove_range_batch_device(uint64_t n, const uint64_t* d_value, const 
     if (!bits_to_lg(n_bits, &lg)) return fail(ZKP_HIP_E_UNSUPPORTED, "n_bits must be 8, 16, 32 or 64");
     if (!d_seeds) return fail(ZKP_HIP_E_ARGUMENT, "device entry point needs seeds");
     Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    if (rc || (rc = ensure_bp())) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : dev().stream;
     rc = prove_range_device_locked(n, d_value, d_min, d_max, lg, d_seeds, d_out, stride, d_out_len, d_status, st, any_failed);
     if (rc) return rc;
@@ -1165,7 +1229,7 @@ int zkp_hip_prove_range_batch(uint64_t n, const uint64_t* value, const uint64_t*
     std::vector<uint8_t> fresh;
     if (!seeds) { int rc0 = fresh_seeds(fresh, n); if (rc0) return rc0; seeds = fresh.data(); }   // bulletproofs.rs:82-87
     Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    if (rc || (rc = ensure_bp())) return rc;
     hipStream_t st = dev().stream;
     DevScope mem;
     uint64_t *d_in = nullptr; uint8_t *d_seeds = nullptr, *d_out = nullptr; uint32_t* d_len = nullptr; int32_t* d_status = nullptr;

@@ -153,6 +153,20 @@ pub fn load_proving_key(kind: i32, pk_bytes: &[u8]) -> ZkpResult<()> {
     Ok(())
 }
 
+/// `zkp_hip_groth16_key_info` kind of the Bulletproofs generator tables (`ZKP_HIP_TABLES_BP_GENERATORS`, include/libzkp_hip.h).
+pub const ZKP_HIP_TABLES_BP_GENERATORS: i32 = 2;
+
+/// The radix (log2) and HBM bytes of the calling thread's shard's Bulletproofs generator tables; `(0, 0)` while
+/// `ZKP_HIP_ED_TABLES=lazy` has not built them yet.
+pub fn generator_table_info() -> ZkpResult<(u32, u64)> {
+    let (mut wbits, mut uneven, mut bytes) = (0u32, 0u32, 0u64);
+    let rc = unsafe { ffi::zkp_hip_groth16_key_info(ZKP_HIP_TABLES_BP_GENERATORS, &mut wbits, &mut uneven, &mut bytes) };
+    if rc != 0 {
+        return Err(ZkpError::ConfigError(ffi::last_error()));
+    }
+    Ok((wbits, bytes))
+}
+
 /// One process drives every GPU of the node: call once at start-up (advanced::process_batch then shards each batch).
 pub fn init_all_gpus(n_gpus: u32) -> ZkpResult<()> {
     let devs: Vec<i32> = (0..n_gpus as i32).collect();
