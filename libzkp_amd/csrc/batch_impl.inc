@@ -196,36 +196,11 @@ extern "C" int zkp_hip_batch_wait(zkp_hip_batch* batch);
 
 namespace {
 
-// runs f(shard k) for every plan on that shard's worker thread (inline when there is one shard); collects the first error.
-// Two plans of one batch never share a Device, but two BATCHES may be fanned out at once from different caller threads (stage of batch
-// N + 1 while another thread waits for batch N): each worker takes jobs in FIFO order and every caller waits for its own tickets, so
-// the captures below outlive their jobs whatever the other callers do.
+// for_each_device over the plans of a batch: f(plan of shard k), bound to that shard (two plans of one batch never share a Device)
 template <class F> int for_each_shard(zkp_hip_batch& B, F f, bool init = true) {
-    const size_t S = B.shards.size();
-    if (S == 1) { Bind bind; int rc = bind.open(B.shards[0].d, init); if (rc) return rc; return f(B.shards[0]); }
-    std::vector<int> rcs(S, 0); std::vector<std::string> errs(S);
-    std::vector<ShardWorker::Ticket> tickets(S);
-    {
-        std::lock_guard<std::mutex> lk(g_worker_create_mu);
-        for (size_t k = 0; k < S; k++) if (!B.shards[k].d->worker) B.shards[k].d->worker = new ShardWorker();
-    }
-    size_t posted = 0;
-    int post_rc = guarded([&]() {
-        for (; posted < S; posted++) {
-            const size_t k = posted;
-            tickets[k] = B.shards[k].d->worker->post([&, k]() {
-                const int rc = guarded([&]() { Bind bind; int r = bind.open(B.shards[k].d, init); return r ? r : f(B.shards[k]); });
-                rcs[k] = rc;
-                if (rc < 0) { try { errs[k] = t_err; } catch (...) {} }
-            });
-        }
-        return 0;
-    });
-    for (size_t k = 0; k < posted; k++) B.shards[k].d->worker->wait(tickets[k]);      // even when a post failed: the jobs hold references to this frame
-    if (post_rc) return post_rc;
-    int any = 0;
-    for (size_t k = 0; k < S; k++) { if (rcs[k] < 0) return fail(rcs[k], errs[k]); any |= rcs[k]; }
-    return any;
+    std::vector<Device*> devs;
+    for (auto& P : B.shards) devs.push_back(P.d);
+    return for_each_device(devs, [&](size_t k) { return f(B.shards[k]); }, init);
 }
 
 uint64_t op_max_bytes(const zkp_hip_op& o) {
@@ -283,15 +258,12 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
         P.max_total += op_max_bytes(o);
         switch (o.kind) {
             case ZKP_HIP_OP_RANGE: P.n_range++; break;
-            case ZKP_HIP_OP_EQUALITY: row_ok[j] = o.a == o.b; P.n_eq += row_ok[j]; break;                       // validation.rs:21-27
-            case ZKP_HIP_OP_MEMBERSHIP: {                                                                        // validation.rs:50-63, snark.rs:406-418
-                bool found = false;
-                if (o.count > 0 && o.count <= G16_MAX_SET) for (uint32_t k = 0; k < o.count; k++) found |= lists[o.list_off + k] == o.a;
-                row_ok[j] = found; P.n_mem += found;
-                if (found && op_max_bytes(o) > P.stride_mem) P.stride_mem = op_max_bytes(o);
+            case ZKP_HIP_OP_EQUALITY: row_ok[j] = equality_ok(o.a, o.b); P.n_eq += row_ok[j]; break;
+            case ZKP_HIP_OP_MEMBERSHIP:
+                row_ok[j] = membership_ok(o.a, lists + o.list_off, o.count); P.n_mem += row_ok[j];
+                if (row_ok[j] && op_max_bytes(o) > P.stride_mem) P.stride_mem = op_max_bytes(o);
                 break;
-            }
-            case ZKP_HIP_OP_IMPROVEMENT: row_ok[j] = o.b > o.a; P.n_imp += row_ok[j]; break;                   // validation.rs:63-71
+            case ZKP_HIP_OP_IMPROVEMENT: row_ok[j] = improvement_ok(o.a, o.b); P.n_imp += row_ok[j]; break;
             case ZKP_HIP_OP_THRESHOLD: P.n_thr++; break;
             default: P.n_con++; if (consistency_envelope_bytes(o.count ? o.count : 1) > P.stride_con) P.stride_con = consistency_envelope_bytes(o.count ? o.count : 1); break;
         }

@@ -149,31 +149,22 @@ extern "C" {
 
 int zkp_hip_verify_range_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !mins || !maxs || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, mins, maxs, ok}, stride);
+    if (rc || (rc = bind.open())) return rc;
     return verify_bp_locked(1, n, proofs, stride, lens, mins, maxs, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_threshold_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* thresholds, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !thresholds || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, thresholds, ok}, stride);
+    if (rc || (rc = bind.open())) return rc;
     return verify_bp_locked(3, n, proofs, stride, lens, thresholds, nullptr, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_consistency_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc || (rc = bind.open())) return rc;
     return verify_bp_locked(6, n, proofs, stride, lens, nullptr, nullptr, ok);
 } ZKP_API_CATCH_INT
 

@@ -776,27 +776,16 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
 // ================================================================================================ C ABI (Groth16 part)
 extern "C" {
 
-// every registered shard gets the key (its tables are built on that shard's GPU, one host thread per shard)
+// every registered shard but `skip` gets the key (its tables are built on that shard's GPU, the shards in parallel)
 static int load_key_all_shards(int kind, const uint8_t* pk, uint64_t len, Device* skip) {
-    std::vector<Device*> devs;
+    std::vector<Device*> todo;
     {
         Device* d0 = nullptr; int rc = find_shard(0, &d0);
         if (rc) return rc;
-        Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); devs = R.shards;
+        Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu);
+        for (Device* d : R.shards) if (d != skip) todo.push_back(d);
     }
-    std::vector<Device*> todo; for (Device* d : devs) if (d != skip) todo.push_back(d);
-    if (todo.empty()) return 0;
-    if (todo.size() == 1) { Bind bind; int rc = bind.open(todo[0]); if (rc) return rc; return load_key_locked(kind, pk, len); }
-    std::vector<int> rcs(todo.size(), 0); std::vector<std::string> errs(todo.size());
-    std::vector<std::thread> th;
-    for (size_t k = 0; k < todo.size(); k++)
-        th.emplace_back([&, k]() {
-            rcs[k] = guarded([&]() { Bind bind; int rc = bind.open(todo[k]); return rc ? rc : load_key_locked(kind, pk, len); });
-            if (rcs[k]) { try { errs[k] = t_err; } catch (...) {} }
-        });
-    for (auto& t : th) t.join();
-    for (size_t k = 0; k < todo.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);
-    return 0;
+    return for_each_device(todo, [&](size_t) { return load_key_locked(kind, pk, len); });
 }
 
 int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len) try {
@@ -844,29 +833,21 @@ int zkp_hip_groth16_generate_key(int kind, const uint8_t* setup_seed, uint8_t* p
 
 int zkp_hip_verify_equality_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc || (rc = bind.open())) return rc;
     return verify_g16_host(G16_EQUALITY, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 int zkp_hip_verify_membership_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc || (rc = bind.open())) return rc;
     return verify_g16_host(G16_MEMBERSHIP, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_snark_commit_value_batch(uint64_t n, const uint64_t* values, uint8_t* out) try {
     if (n == 0) return 0;
-    if (!values || !out) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
+    Bind bind; int rc = host_args(n, {values, out});
+    if (rc || (rc = bind.open())) return rc;
     if (!g16s().mimc_dev) {
         ensure_mimc_constants();
         std::vector<uint32_t> mc; for (auto& c : g_mimc_host) put_fr(mc, c);
@@ -885,33 +866,26 @@ int zkp_hip_snark_commit_value_batch(uint64_t n, const uint64_t* values, uint8_t
 int zkp_hip_prove_equality_batch(uint64_t n, const uint64_t* val1, const uint64_t* val2, const uint8_t* seeds,
                                  uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status) try {
     if (n == 0) return 0;
-    if (!val1 || !val2 || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    if (stride < 298) return fail(ZKP_HIP_E_ARGUMENT, "stride must be >= 298");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
     std::vector<uint8_t> fresh;
-    if (!seeds) { int rc0 = fresh_seeds(fresh, n); if (rc0) return rc0; seeds = fresh.data(); }
-    std::vector<uint8_t> valid(n);
-    for (uint64_t i = 0; i < n; i++) valid[i] = val1[i] == val2[i];          // validation.rs:21-27
-    Bind bind; int rc = bind.open();
+    int rc = prover_args(fresh, seeds, n, {val1, val2, out, out_len, status}, nullptr, stride, 298, "stride must be >= 298");
     if (rc) return rc;
+    std::vector<uint8_t> valid(n);
+    for (uint64_t i = 0; i < n; i++) valid[i] = equality_ok(val1[i], val2[i]);
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return prove_g16_host(G16_EQUALITY, n, val1, nullptr, nullptr, valid, seeds, out, stride, out_len, status);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_prove_membership_batch(uint64_t n, const uint64_t* values, const uint64_t* sets, const uint32_t* set_counts, const uint8_t* seeds,
                                    uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status) try {
     if (n == 0) return 0;
-    if (!values || !sets || !set_counts || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn || (rcn = check_list_total(n, set_counts))) return rcn; }
     std::vector<uint8_t> fresh;
-    if (!seeds) { int rc0 = fresh_seeds(fresh, n); if (rc0) return rc0; seeds = fresh.data(); }
-    std::vector<uint8_t> valid(n); size_t pos = 0;
-    for (uint64_t i = 0; i < n; i++) {                                      // validation.rs:50-63, snark.rs:406-418
-        const uint32_t c = set_counts[i]; bool ok = c > 0 && c <= G16_MAX_SET, found = false;
-        for (uint32_t k = 0; k < c; k++) found |= sets[pos + k] == values[i];
-        valid[i] = ok && found; pos += c;
-    }
-    Bind bind; int rc = bind.open();
+    int rc = prover_args(fresh, seeds, n, {values, sets, set_counts, out, out_len, status}, set_counts);
     if (rc) return rc;
+    std::vector<uint8_t> valid(n);
+    for (uint64_t i = 0, pos = 0; i < n; pos += set_counts[i++]) valid[i] = membership_ok(values[i], sets + pos, set_counts[i]);
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return prove_g16_host(G16_MEMBERSHIP, n, values, sets, set_counts, valid, seeds, out, stride, out_len, status);
 } ZKP_API_CATCH_INT
 

@@ -32,12 +32,8 @@ uint32_t zkp_hip_improvement_max_bytes(void) { return STARK_MAX_ENVELOPE; }     
 int zkp_hip_prove_improvement_batch_device(uint64_t n, const uint64_t* d_old, const uint64_t* d_new, uint8_t* d_out, uint64_t stride,
                                            uint32_t* d_out_len, void* stream) try {
     if (n == 0) return 0;
-    if (!d_old || !d_new || !d_out || !d_out_len) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride < STARK_MAX_ENVELOPE) return fail(ZKP_HIP_E_ARGUMENT, "stride must be at least zkp_hip_improvement_max_bytes()");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
-    if ((rc = ensure_stark_constants())) return rc;
+    Bind bind; int rc = host_args(n, {d_old, d_new, d_out, d_out_len}, nullptr, stride, STARK_MAX_ENVELOPE, "stride must be at least zkp_hip_improvement_max_bytes()");
+    if (rc || (rc = bind.open()) || (rc = ensure_stark_constants())) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : dev().stream;
     stark_launch_prove(d_old, d_new, (uint32_t)n, g_stark_const, d_out, stride, d_out_len, st);
     HIP_TRY(hipGetLastError());
@@ -48,12 +44,9 @@ int zkp_hip_prove_improvement_batch_device(uint64_t n, const uint64_t* d_old, co
 int zkp_hip_prove_improvement_batch(uint64_t n, const uint64_t* old_values, const uint64_t* new_values, uint8_t* out, uint64_t stride,
                                     uint32_t* out_len, int32_t* status) try {
     if (n == 0) return 0;
-    if (!old_values || !new_values || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride < STARK_MAX_ENVELOPE) return fail(ZKP_HIP_E_ARGUMENT, "stride must be at least zkp_hip_improvement_max_bytes()");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
-    if ((rc = ensure_stark_constants())) return rc;
+    Bind bind; int rc = host_args(n, {old_values, new_values, out, out_len, status}, nullptr, stride, STARK_MAX_ENVELOPE,
+                                  "stride must be at least zkp_hip_improvement_max_bytes()");
+    if (rc || (rc = bind.open()) || (rc = ensure_stark_constants())) return rc;
     hipStream_t st = dev().stream;
     uint64_t *d_old = nullptr, *d_new = nullptr; uint8_t* d_out = nullptr; uint32_t* d_len = nullptr;
     DevScope mem;
@@ -69,8 +62,7 @@ int zkp_hip_prove_improvement_batch(uint64_t n, const uint64_t* old_values, cons
     if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
     int any = 0;
     for (uint64_t i = 0; i < n; i++) {
-        // validate_improvement_params (utils/validation.rs:63-71): "new value must be greater than old value"
-        if (new_values[i] <= old_values[i]) { status[i] = ZKP_HIP_INVALID_INPUT; out_len[i] = 0; any = 1; }
+        if (!improvement_ok(old_values[i], new_values[i])) { status[i] = ZKP_HIP_INVALID_INPUT; out_len[i] = 0; any = 1; }
         else if (out_len[i] == 0) { status[i] = ZKP_HIP_PROOF_GENERATION_FAILED; any = 1; }
         else status[i] = ZKP_HIP_OK;
     }
@@ -79,12 +71,8 @@ int zkp_hip_prove_improvement_batch(uint64_t n, const uint64_t* old_values, cons
 
 int zkp_hip_verify_improvement_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* old_values, uint8_t* ok) try {
     if (n == 0) return 0;
-    if (!proofs || !lens || !old_values || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride == 0) return fail(ZKP_HIP_E_ARGUMENT, "bad stride");
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
-    if ((rc = ensure_stark_constants())) return rc;
+    Bind bind; int rc = verifier_args(n, {proofs, lens, old_values, ok}, stride);
+    if (rc || (rc = bind.open()) || (rc = ensure_stark_constants())) return rc;
     hipStream_t st = dev().stream;
     uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t* d_old = nullptr;
     DevScope mem;

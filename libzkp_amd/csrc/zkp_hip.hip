@@ -185,7 +185,7 @@ int fail_nothrow(int code, const char* what, const char* detail) noexcept {
 #define ZKP_API_CATCH_INT ZKP_API_CATCH_RET(return ZKP_HIP_E_RUNTIME)
 #define ZKP_API_CATCH_ZERO ZKP_API_CATCH_RET(return 0)
 #define ZKP_API_CATCH_VOID ZKP_API_CATCH_RET(return)
-// the same for the body of a host worker thread (an exception that leaves a std::thread's function is std::terminate)
+// the same for the body of a host worker thread (an exception that leaves a thread's function is std::terminate)
 template <class F> int guarded(F&& f) noexcept {
     try { return f(); }
     catch (const std::bad_alloc&) { return fail_nothrow(ZKP_HIP_E_RUNTIME, "out of host memory", nullptr); }
@@ -333,9 +333,10 @@ struct Device {
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
 };
-// One parked host thread per shard: a multi-shard batch call (stage, prove, fetch = three fan-outs per batch) hands each shard's share to
-// that shard's worker instead of creating and joining a std::thread per shard per fan-out.  The thread touches HIP only inside a job; it is
-// never joined (nothing of this library is destroyed from exit(), see the registry below) and survives zkp_hip_shutdown parked.
+// One parked host thread per shard, the only host threads of the library: every call that works on several shards at once -- a multi-shard
+// batch (stage, prove, fetch = three fan-outs per batch), zkp_hip_init_devices, loading a key on every shard -- hands each shard's part to
+// that shard's worker through for_each_device instead of creating and joining a thread per shard.  The thread touches HIP only inside a
+// job; it is never joined (nothing of this library is destroyed from exit(), see the registry below) and survives zkp_hip_shutdown parked.
 struct ShardWorker {
     // A FIFO of jobs, each with its own completion flag: callers on different host threads (one staging batch N + 1 while another waits
     // for batch N) may post to the same shard's worker at once; every caller waits for ITS tickets only, so no job is overwritten and
@@ -350,7 +351,7 @@ struct ShardWorker {
         for (;;) {
             Ticket t;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this]() { return !queue.empty(); }); t = queue.front(); queue.pop_front(); }
-            t->fn();                                   // (posted bodies never throw: for_each_shard wraps them in guarded())
+            t->fn();                                   // (posted bodies never throw: for_each_device wraps them in guarded())
             { std::lock_guard<std::mutex> lk(mu); t->done = true; }
             cv.notify_all();
         }
@@ -369,7 +370,7 @@ int prof_begin(Device::KProf& K, hipStream_t st, hipEvent_t* e1);
 void prof_end(Device::KProf& K, hipStream_t st, hipEvent_t e1, uint64_t adds);
 // Everything below is allocated once and never destroyed: no destructor of this library runs from exit() (the HIP
 // runtime and profiler tools tear themselves down there in an order we do not control); device resources are released
-// by zkp_hip_shutdown, which an atexit hook registered at the first initialisation calls while the runtime is alive.
+// by zkp_hip_shutdown, which an atexit hook armed at the first registration (register_shards_locked) calls while the runtime is alive.
 struct Registry {
     std::mutex mu;
     std::vector<Device*> shards;
@@ -698,52 +699,60 @@ int init_device() {
     D.ready = true;
     return 0;
 }
+// destroys what a slot holds -- workspace, events, and its streams unless they are slot 0's (`borrowed`) -- and empties it
+void release_sub(SubBatch& sb) {
+    if (sb.ws) (void)hipFree(sb.ws);
+    for (hipEvent_t e : {sb.start, sb.done, sb.side_go, sb.side_done}) if (e) (void)hipEventDestroy(e);
+    if (!sb.borrowed) { if (sb.stream) (void)hipStreamDestroy(sb.stream); if (sb.side) (void)hipStreamDestroy(sb.side); }
+    sb = SubBatch();
+}
 // `share`: take the streams of that slot instead of creating a pair.  The second slot of a shard (the second of two batches in flight)
 // is a second workspace on the SAME streams: its chain queues behind the first batch's chain of the same variant, which is the overlap
 // one wants -- the tail of one batch under the head of the next -- without a second set of hardware queues (with its own streams the
 // second lane shared queues with the first one's, and two batches in flight measured slower than one: 15.1 against 13.6 ms per batch).
 int ensure_sub(SubBatch& sb, SubBatch* share = nullptr) {
     if (sb.stream) return 0;
-    // Built in locals and committed to `sb` only when every object exists: a failure half-way (these are created lazily, in the middle of
-    // a batch enqueue) must not leave a slot that looks ready but holds null events.
-    hipStream_t stream = nullptr, side = nullptr; bool borrowed = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto undo = [&]() {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        if (!borrowed) { if (stream) (void)hipStreamDestroy(stream); if (side) (void)hipStreamDestroy(side); }
-    };
+    // Built in a local slot and committed to `sb` only when every object exists: a failure half-way (these are created lazily, in the
+    // middle of a batch enqueue) must not leave a slot that looks ready but holds null events.
+    SubBatch t;
     int rc = 0;
     if (share && share != &sb) {
         if ((rc = ensure_sub(*share))) return rc;
-        stream = share->stream; side = share->side; borrowed = true;
+        t.stream = share->stream; t.side = share->side; t.borrowed = true;
     } else {
-        hipError_t e = hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, stream_priority(bp_priority_level()));
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, stream_priority(bp_priority_level()));
-        if (e != hipSuccess) { undo(); return fail(ZKP_HIP_E_RUNTIME, std::string("hipStreamCreateWithPriority: ") + hipGetErrorString(e)); }
+        hipError_t e = hipStreamCreateWithPriority(&t.stream, hipStreamNonBlocking, stream_priority(bp_priority_level()));
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&t.side, hipStreamNonBlocking, stream_priority(bp_priority_level()));
+        if (e != hipSuccess) { release_sub(t); return fail(ZKP_HIP_E_RUNTIME, std::string("hipStreamCreateWithPriority: ") + hipGetErrorString(e)); }
     }
-    for (auto& e : ev) {
-        const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        if (err != hipSuccess) { e = nullptr; undo(); return fail(ZKP_HIP_E_RUNTIME, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(err)); }
+    for (hipEvent_t* e : {&t.start, &t.done, &t.side_go, &t.side_done}) {
+        const hipError_t err = hipEventCreateWithFlags(e, hipEventDisableTiming);
+        if (err != hipSuccess) { *e = nullptr; release_sub(t); return fail(ZKP_HIP_E_RUNTIME, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(err)); }
     }
-    sb.start = ev[0]; sb.done = ev[1]; sb.side_go = ev[2]; sb.side_done = ev[3];
-    sb.side = side; sb.borrowed = borrowed; sb.stream = stream;
+    sb.start = t.start; sb.done = t.done; sb.side_go = t.side_go; sb.side_done = t.side_done;
+    sb.side = t.side; sb.borrowed = t.borrowed; sb.stream = t.stream;
     return 0;
 }
 
 extern "C" void zkp_hip_shutdown(void);
 void batch_release_all();
 void stark_release_all();
+// The one place shards come into being (caller holds R.mu): checks that HIP sees a device and that every one of devices[0..count) exists
+// (else `bad_index`), appends one shard per entry when `add`, and arms the atexit hook once.
+int register_shards_locked(Registry& R, const int* devices, uint32_t count, bool add, const char* bad_index) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(ZKP_HIP_E_RUNTIME, "zkp_hip_init: no HIP device available (this library has no CPU fallback)");
+    for (uint32_t k = 0; k < count; k++) if (devices[k] < 0 || devices[k] >= ndev) return fail(ZKP_HIP_E_ARGUMENT, bad_index);
+    for (uint32_t k = 0; add && k < count; k++) { Device* d = new Device(); d->index = (int)R.shards.size(); d->hip_dev = devices[k]; R.shards.push_back(d); }
+    if (!R.hooked) { R.hooked = true; (void)atexit(zkp_hip_shutdown); }
+    return 0;
+}
 // shard `index` of the registry; registers shard 0 on HIP device 0 when nothing has been registered yet
 int find_shard(int index, Device** out) {
     Registry& R = registry();
     std::lock_guard<std::mutex> lk(R.mu);
-    if (R.shards.empty()) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            return fail(ZKP_HIP_E_RUNTIME, "zkp_hip_init: no HIP device available (this library has no CPU fallback)");
-        Device* d = new Device(); d->index = 0; d->hip_dev = 0; R.shards.push_back(d);
-    }
-    if (!R.hooked) { R.hooked = true; (void)atexit(zkp_hip_shutdown); }
+    const int device0 = 0;
+    if (R.shards.empty()) { int rc = register_shards_locked(R, &device0, 1, true, "zkp_hip_init: bad device index"); if (rc) return rc; }
     if (index < 0 || index >= (int)R.shards.size()) return fail(ZKP_HIP_E_ARGUMENT, "no such device shard (zkp_hip_init / zkp_hip_init_devices register them)");
     *out = R.shards[index];
     return 0;
@@ -771,6 +780,38 @@ struct Bind {
     }
     ~Bind() { if (bound) t_dev = prev; }
 };
+
+// Runs f(k) bound to devs[k] (Bind::open(devs[k], init)) for every k and waits for all of them: on the calling thread when there is one
+// target, otherwise on the shards' ShardWorkers.  Two calls may fan out at once from different threads (stage of batch N + 1 while another
+// thread waits for batch N): each worker takes jobs in FIFO order and every caller waits for its own tickets, so the captures below outlive
+// their jobs whatever the other callers do.  A negative code is the lowest-numbered failing target's, with its message; positive codes OR.
+template <class F> int for_each_device(const std::vector<Device*>& devs, F f, bool init = true) {
+    const size_t S = devs.size();
+    if (S == 1) { Bind bind; int rc = bind.open(devs[0], init); if (rc) return rc; return f((size_t)0); }
+    std::vector<int> rcs(S, 0); std::vector<std::string> errs(S);
+    std::vector<ShardWorker::Ticket> tickets(S);
+    {
+        std::lock_guard<std::mutex> lk(g_worker_create_mu);
+        for (Device* d : devs) if (!d->worker) d->worker = new ShardWorker();
+    }
+    size_t posted = 0;
+    int post_rc = guarded([&]() {
+        for (; posted < S; posted++) {
+            const size_t k = posted;
+            tickets[k] = devs[k]->worker->post([&, k]() {
+                const int rc = guarded([&]() { Bind bind; int r = bind.open(devs[k], init); return r ? r : f(k); });
+                rcs[k] = rc;
+                if (rc < 0) { try { errs[k] = t_err; } catch (...) {} }
+            });
+        }
+        return 0;
+    });
+    for (size_t k = 0; k < posted; k++) devs[k]->worker->wait(tickets[k]);      // even when a post failed: the jobs hold references to this frame
+    if (post_rc) return post_rc;
+    int any = 0;
+    for (size_t k = 0; k < S; k++) { if (rcs[k] < 0) return fail(rcs[k], errs[k]); any |= rcs[k]; }
+    return any;
+}
 
 // workspace carving ---------------------------------------------------------------------------------
 struct Ws {
@@ -1009,6 +1050,44 @@ int fresh_seeds(std::vector<uint8_t>& buf, size_t n) {
     return 0;
 }
 
+// Argument checks of the host-buffer entry points, all before any shard is looked up (an absurd size is an argument error, not an
+// allocation or a device lookup), in this order: a null pointer among `ptrs`, the batch size, the summed list lengths when `counts` is
+// given, stride >= min_stride.  The caller has returned for n == 0 already.
+int host_args(uint64_t n, std::initializer_list<const void*> ptrs, const uint32_t* counts = nullptr, uint64_t stride = 0, uint64_t min_stride = 0,
+              const char* stride_msg = "") {
+    for (const void* p : ptrs) if (!p) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    int rc = check_batch_size(n);
+    if (rc || (counts && (rc = check_list_total(n, counts)))) return rc;
+    if (stride < min_stride) return fail(ZKP_HIP_E_ARGUMENT, stride_msg);
+    return 0;
+}
+// a prover's: the same checks, then fresh seeds in `fresh` when the caller passed none (bulletproofs.rs:82-87)
+int prover_args(std::vector<uint8_t>& fresh, const uint8_t*& seeds, uint64_t n, std::initializer_list<const void*> ptrs, const uint32_t* counts = nullptr,
+                uint64_t stride = 0, uint64_t min_stride = 0, const char* stride_msg = "") {
+    int rc = host_args(n, ptrs, counts, stride, min_stride, stride_msg);
+    if (rc || seeds) return rc;
+    if ((rc = fresh_seeds(fresh, n))) return rc;
+    seeds = fresh.data();
+    return 0;
+}
+// a verifier's: envelopes of `stride` bytes, zero refused
+int verifier_args(uint64_t n, std::initializer_list<const void*> ptrs, uint64_t stride) { return host_args(n, ptrs, nullptr, stride, 1, "bad stride"); }
+
+// The reference's validation rules (utils/validation.rs), one predicate each, for the per-variant entry points and the batch scheduler
+// (stage_shard) alike.  The threshold rule is frame_threshold's.
+bool equality_ok(uint64_t a, uint64_t b) { return a == b; }                                 // validation.rs:21-26
+bool membership_ok(uint64_t value, const uint64_t* set, uint32_t count) {                 // validation.rs:47-60; sets of at most 64 (snark.rs:406-418)
+    if (count == 0 || count > G16_MAX_SET) return false;
+    for (uint32_t k = 0; k < count; k++) if (set[k] == value) return true;
+    return false;
+}
+bool improvement_ok(uint64_t old_value, uint64_t new_value) { return new_value > old_value; }     // validation.rs:63-71
+bool consistency_ok(const uint64_t* list, uint32_t count) {                                  // validation.rs:74-86: not empty, non-decreasing
+    if (count == 0) return false;
+    for (uint32_t j = 1; j < count; j++) if (list[j - 1] > list[j]) return false;
+    return true;
+}
+
 uint64_t threshold_envelope_bytes(uint32_t lg) { return 10 + 8 + 4 + 4 + rp_bytes(lg) + 32 + 32; }      // 762 for n_bits = 64
 uint64_t consistency_envelope_bytes(uint32_t count) {
     if (count == 0) return 0;
@@ -1046,8 +1125,7 @@ int frame_consistency(uint64_t n, const uint64_t* data, const uint32_t* counts, 
     int any = 0; size_t pos = 0;
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t k = counts[i]; const uint64_t* d = data + pos; pos += k;
-        bool ok = k > 0;                                            // validation.rs:75-88
-        for (uint32_t j = 1; j < k && ok; j++) if (d[j - 1] > d[j]) ok = false;
+        bool ok = consistency_ok(d, k);
         const uint64_t need = consistency_envelope_bytes(k);
         if (ok && need > stride) ok = false;                        // (callers size the stride from the counts; never reached through the ABI)
         status[i] = ok ? ZKP_HIP_OK : ZKP_HIP_INVALID_INPUT; out_len[i] = ok ? (uint32_t)need : 0; any |= !ok;
@@ -1086,13 +1164,10 @@ int zkp_hip_init(int device) try {
     {
         Registry& R = registry();
         std::lock_guard<std::mutex> lk(R.mu);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            return fail(ZKP_HIP_E_RUNTIME, "zkp_hip_init: no HIP device available (this library has no CPU fallback)");
-        if (device < 0 || device >= ndev) return fail(ZKP_HIP_E_ARGUMENT, "zkp_hip_init: bad device index");
-        for (Device* s : R.shards) if (s->hip_dev == device) { d = s; break; }
-        if (!d) { d = new Device(); d->index = (int)R.shards.size(); d->hip_dev = device; R.shards.push_back(d); }
-        if (!R.hooked) { R.hooked = true; (void)atexit(zkp_hip_shutdown); }
+        for (Device* s : R.shards) if (s->hip_dev == device) { d = s; break; }       // a shard already on `device` is reused
+        int rc = register_shards_locked(R, &device, 1, !d, "zkp_hip_init: bad device index");
+        if (rc) return rc;
+        if (!d) d = R.shards.back();
     }
     Bind bind; int rc = bind.open(d);
     return rc;
@@ -1104,26 +1179,14 @@ int zkp_hip_init_devices(uint32_t count, const int* devices) try {
     {
         Registry& R = registry();
         std::lock_guard<std::mutex> lk(R.mu);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            return fail(ZKP_HIP_E_RUNTIME, "zkp_hip_init: no HIP device available (this library has no CPU fallback)");
-        for (uint32_t k = 0; k < count; k++) if (devices[k] < 0 || devices[k] >= ndev) return fail(ZKP_HIP_E_ARGUMENT, "zkp_hip_init_devices: bad device index");
-        if (!R.shards.empty()) {                       // idempotent for the same assignment; anything else needs a shutdown first
-            bool same = R.shards.size() == count;
-            for (uint32_t k = 0; same && k < count; k++) same = R.shards[k]->hip_dev == devices[k];
-            if (!same) return fail(ZKP_HIP_E_ARGUMENT, "zkp_hip_init_devices: shards are already registered differently (zkp_hip_shutdown first)");
-        } else {
-            for (uint32_t k = 0; k < count; k++) { Device* d = new Device(); d->index = (int)k; d->hip_dev = devices[k]; R.shards.push_back(d); }
-        }
+        int rc = register_shards_locked(R, devices, count, R.shards.empty(), "zkp_hip_init_devices: bad device index");
+        if (rc) return rc;
+        bool same = R.shards.size() == count;          // idempotent for the same assignment; anything else needs a shutdown first
+        for (uint32_t k = 0; same && k < count; k++) same = R.shards[k]->hip_dev == devices[k];
+        if (!same) return fail(ZKP_HIP_E_ARGUMENT, "zkp_hip_init_devices: shards are already registered differently (zkp_hip_shutdown first)");
         mine = R.shards;
-        if (!R.hooked) { R.hooked = true; (void)atexit(zkp_hip_shutdown); }
     }
-    std::vector<int> rcs(count, 0); std::vector<std::string> errs(count);
-    std::vector<std::thread> th;
-    for (uint32_t k = 0; k < count; k++) th.emplace_back([&, k]() { rcs[k] = guarded([&]() { Bind bind; return bind.open(mine[k]); }); if (rcs[k]) { try { errs[k] = t_err; } catch (...) {} } });
-    for (auto& t : th) t.join();
-    for (uint32_t k = 0; k < count; k++) if (rcs[k]) return fail(rcs[k], errs[k]);
-    return 0;
+    return for_each_device(mine, [](size_t) { return 0; });          // Bind::open initialises each shard
 } ZKP_API_CATCH_INT
 
 int zkp_hip_device_count(void) try { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); return (int)R.shards.size(); } ZKP_API_CATCH_INT
@@ -1153,14 +1216,7 @@ void zkp_hip_shutdown(void) try {
         bpv_release_all();
         stark_release_all();
         d->pool.release_all();
-        for (auto& sb : d->sub) {
-            if (sb.ws) (void)hipFree(sb.ws);
-            if (sb.stream) {
-                if (!sb.borrowed) { (void)hipStreamDestroy(sb.stream); (void)hipStreamDestroy(sb.side); }
-                (void)hipEventDestroy(sb.start); (void)hipEventDestroy(sb.done); (void)hipEventDestroy(sb.side_go); (void)hipEventDestroy(sb.side_done);
-            }
-            sb = SubBatch();
-        }
+        for (auto& sb : d->sub) release_sub(sb);
         d->msm_prio_now = 0;
         release_edg_table();
         free_set(d->p2); free_set(d->ct);
@@ -1223,13 +1279,11 @@ int zkp_hip_prove_range_batch(uint64_t n, const uint64_t* value, const uint64_t*
     uint32_t lg;
     if (!bits_to_lg(n_bits, &lg)) return fail(ZKP_HIP_E_UNSUPPORTED, "n_bits must be 8, 16, 32 or 64");
     if (n == 0) return 0;
-    if (!value || !min || !max || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn) return rcn; }
-    if (stride < range_envelope_bytes(lg)) return fail(ZKP_HIP_E_ARGUMENT, "stride is smaller than the proof (1478 bytes for n_bits = 64)");
     std::vector<uint8_t> fresh;
-    if (!seeds) { int rc0 = fresh_seeds(fresh, n); if (rc0) return rc0; seeds = fresh.data(); }   // bulletproofs.rs:82-87
-    Bind bind; int rc = bind.open();
-    if (rc || (rc = ensure_bp())) return rc;
+    int rc = prover_args(fresh, seeds, n, {value, min, max, out, out_len, status}, nullptr, stride, range_envelope_bytes(lg),
+                         "stride is smaller than the proof (1478 bytes for n_bits = 64)");
+    Bind bind;
+    if (rc || (rc = bind.open()) || (rc = ensure_bp())) return rc;
     hipStream_t st = dev().stream;
     DevScope mem;
     uint64_t *d_in = nullptr; uint8_t *d_seeds = nullptr, *d_out = nullptr; uint32_t* d_len = nullptr; int32_t* d_status = nullptr;
@@ -1265,40 +1319,33 @@ int zkp_hip_prove_threshold_batch(uint64_t n, const uint64_t* values, const uint
     uint32_t lg;
     if (!bits_to_lg(n_bits, &lg)) return fail(ZKP_HIP_E_UNSUPPORTED, "n_bits must be 8, 16, 32 or 64");
     if (n == 0) return 0;
-    if (!values || !counts || !thresholds || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn || (rcn = check_list_total(n, counts))) return rcn; }
-    if (stride < threshold_envelope_bytes(lg)) return fail(ZKP_HIP_E_ARGUMENT, "stride is smaller than the proof (762 bytes for n_bits = 64)");
     std::vector<uint8_t> fresh;
-    if (!seeds) { int rc = fresh_seeds(fresh, n); if (rc) return rc; seeds = fresh.data(); }
+    int rc = prover_args(fresh, seeds, n, {values, counts, thresholds, out, out_len, status}, counts, stride, threshold_envelope_bytes(lg),
+                         "stride is smaller than the proof (762 bytes for n_bits = 64)");
+    if (rc) return rc;
     HostJobs H;
     memset(out, 0, stride * n);
     const int any = frame_threshold(n, values, counts, thresholds, lg, out, stride, out_len, status, H);
-    Bind bind; int rc = bind.open();
-    if (rc) return rc;
-    if ((rc = run_host_jobs(H, seeds, n, out, stride * n, lg))) return rc;
+    Bind bind;
+    if ((rc = bind.open()) || (rc = run_host_jobs(H, seeds, n, out, stride * n, lg))) return rc;
     return any;
 } ZKP_API_CATCH_INT
 
 int zkp_hip_prove_consistency_batch(uint64_t n, const uint64_t* data, const uint32_t* counts, const uint8_t* seeds,
                                     uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status) try {
     if (n == 0) return 0;
-    if (!data || !counts || !out || !out_len || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    { int rcn = check_batch_size(n); if (rcn || (rcn = check_list_total(n, counts))) return rcn; }
     std::vector<uint8_t> fresh;
-    if (!seeds) { int rc = fresh_seeds(fresh, n); if (rc) return rc; seeds = fresh.data(); }
-    size_t pos = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        bool ok = counts[i] > 0; for (uint32_t j = 1; j < counts[i] && ok; j++) if (data[pos + j - 1] > data[pos + j]) ok = false;
-        if (ok && zkp_hip_consistency_proof_bytes(counts[i]) > stride) return fail(ZKP_HIP_E_ARGUMENT, "stride too small for a consistency proof (see zkp_hip_consistency_proof_bytes)");
-        pos += counts[i];
-    }
+    int rc = prover_args(fresh, seeds, n, {data, counts, out, out_len, status}, counts);
+    if (rc) return rc;
+    for (uint64_t i = 0, pos = 0; i < n; pos += counts[i++])
+        if (consistency_ok(data + pos, counts[i]) && consistency_envelope_bytes(counts[i]) > stride)
+            return fail(ZKP_HIP_E_ARGUMENT, "stride too small for a consistency proof (see zkp_hip_consistency_proof_bytes)");
     HostJobs H;
     memset(out, 0, stride * n);
     const int any = frame_consistency(n, data, counts, out, stride, out_len, status, H);
     {
-        Bind bind; int rc = bind.open();
-        if (rc) return rc;
-        if ((rc = run_host_jobs(H, seeds, n, out, stride * n))) return rc;
+        Bind bind;
+        if ((rc = bind.open()) || (rc = run_host_jobs(H, seeds, n, out, stride * n))) return rc;
     }
     for (uint64_t i = 0; i < n; i++) {          // commitment field = SHA-256 of the commitment list (bulletproofs.rs:430-436)
         if (status[i] != 0) continue;

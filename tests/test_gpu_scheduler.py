@@ -45,11 +45,13 @@ def _run(L, ops, lists, seeds, cap=None):
     return rc, [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)], st, off
 
 
-def _per_variant(L, ops, lists, seeds):
-    """The same ops through the per-variant entry points (the composition the scheduler must reproduce byte for byte)."""
+def _per_variant(L, ops, lists, seeds, status=None):
+    """The same ops through the per-variant entry points (the composition the scheduler must reproduce byte for byte); their
+    per-op statuses go to `status` when it is given."""
     n = len(ops)
     sd = seeds.reshape(n, 32)
     res = [None] * n
+    status = np.zeros(n, dtype=np.int32) if status is None else status
     k = ops["kind"]
     ix = np.nonzero(k == wl.OP_RANGE)[0]
     if len(ix):
@@ -57,14 +59,14 @@ def _per_variant(L, ops, lists, seeds):
         a, b, c, s = ops["a"][ix].copy(), ops["b"][ix].copy(), ops["c"][ix].copy(), np.ascontiguousarray(sd[ix])
         assert L.zkp_hip_prove_range_batch(m, P(a), P(b), P(c), 64, P(s), P(o), 1478, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     ix = np.nonzero(k == wl.OP_EQUALITY)[0]
     if len(ix):
         m = len(ix); o = np.zeros((m, 298), dtype=np.uint8); ln = np.zeros(m, dtype=np.uint32); st = np.zeros(m, dtype=np.int32)
         a, b, s = ops["a"][ix].copy(), ops["b"][ix].copy(), np.ascontiguousarray(sd[ix])
         assert L.zkp_hip_prove_equality_batch(m, P(a), P(b), P(s), P(o), 298, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     ix = np.nonzero(k == wl.OP_MEMBERSHIP)[0]
     if len(ix):
         m = len(ix); stride = 10 + 4 + 8 * 64 + 256 + 32
@@ -73,14 +75,14 @@ def _per_variant(L, ops, lists, seeds):
         flat = np.concatenate([lists[int(ops["list_off"][i]):int(ops["list_off"][i]) + int(ops["count"][i])] for i in ix] + [np.zeros(1, dtype=np.uint64)])
         assert L.zkp_hip_prove_membership_batch(m, P(a), P(flat), P(cnt), P(s), P(o), stride, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     ix = np.nonzero(k == wl.OP_IMPROVEMENT)[0]
     if len(ix):
         m = len(ix); o = np.zeros((m, 3527), dtype=np.uint8); ln = np.zeros(m, dtype=np.uint32); st = np.zeros(m, dtype=np.int32)
         a, b = ops["a"][ix].copy(), ops["b"][ix].copy()
         assert L.zkp_hip_prove_improvement_batch(m, P(a), P(b), P(o), 3527, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     ix = np.nonzero(k == wl.OP_THRESHOLD)[0]
     if len(ix):
         m = len(ix); o = np.zeros((m, 762), dtype=np.uint8); ln = np.zeros(m, dtype=np.uint32); st = np.zeros(m, dtype=np.int32)
@@ -88,7 +90,7 @@ def _per_variant(L, ops, lists, seeds):
         flat = np.concatenate([lists[int(ops["list_off"][i]):int(ops["list_off"][i]) + int(ops["count"][i])] for i in ix] + [np.zeros(1, dtype=np.uint64)])
         assert L.zkp_hip_prove_threshold_batch(m, P(flat), P(cnt), P(th), 64, P(s), P(o), 762, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     ix = np.nonzero(k == wl.OP_CONSISTENCY)[0]
     if len(ix):
         m = len(ix); cnt = ops["count"][ix].copy(); stride = int(max(L.zkp_hip_consistency_proof_bytes(int(c)) for c in cnt))
@@ -97,7 +99,7 @@ def _per_variant(L, ops, lists, seeds):
         flat = np.concatenate([lists[int(ops["list_off"][i]):int(ops["list_off"][i]) + int(ops["count"][i])] for i in ix] + [np.zeros(1, dtype=np.uint64)])
         assert L.zkp_hip_prove_consistency_batch(m, P(flat), P(cnt), P(s), P(o), stride, P(ln), P(st)) >= 0
         for j, i in enumerate(ix):
-            res[i] = o[j, :ln[j]].tobytes()
+            res[i] = o[j, :ln[j]].tobytes(); status[i] = st[j]
     return res
 
 
@@ -142,18 +144,52 @@ def _six_kind_batch(n, seed):
     return ops, np.array(lists + [0], dtype=np.uint64), wl.op_seeds(seed, n)
 
 
+def _boundary_batch(seed):
+    """The edges of the validation rules (validation.rs), each next to a valid op of its kind; returns the ops that must fail too."""
+    rows, lists, bad = [], [], []
+
+    def op(kind, a=0, b=0, c=0, values=None, invalid=False):
+        count = 0 if values is None else len(values)
+        if invalid:
+            bad.append(len(rows))
+        rows.append((kind, count, a, b, c, len(lists)))
+        lists.extend(values or [])
+
+    big = list(range(1000, 1065))                                     # 65 elements
+    op(wl.OP_RANGE, 5, 0, 100)
+    op(wl.OP_EQUALITY, 7, 7)
+    op(wl.OP_MEMBERSHIP, 3, values=[], invalid=True)                  # empty set
+    op(wl.OP_MEMBERSHIP, 1064, values=big, invalid=True)              # 65 elements: more than a set may hold
+    op(wl.OP_MEMBERSHIP, 1063, values=big[:64])                       # 64 elements, value last
+    op(wl.OP_MEMBERSHIP, 9, values=[9])
+    op(wl.OP_THRESHOLD, 0, values=[], invalid=True)                   # no values
+    op(wl.OP_THRESHOLD, 12, values=[12])                              # sum == threshold
+    op(wl.OP_CONSISTENCY, values=[], invalid=True)                    # empty list
+    op(wl.OP_CONSISTENCY, values=[42])                                # one element: a commitment, no proof
+    op(wl.OP_CONSISTENCY, values=[8, 8])                              # equal neighbours are non-decreasing
+    op(wl.OP_IMPROVEMENT, 50, 50, invalid=True)                       # b == a
+    op(wl.OP_IMPROVEMENT, 50, 49, invalid=True)                       # b < a
+    op(wl.OP_IMPROVEMENT, 50, 51)
+    ops = np.array(rows, dtype=wl.OP_DTYPE)
+    return (ops, np.array(lists + [0], dtype=np.uint64), wl.op_seeds(seed, len(ops))), bad
+
+
 def test_scheduler_equals_per_variant_calls_on_all_six_kinds():
     L = _lib()
-    ops, lists, seeds = _six_kind_batch(180, 11)
-    rc, got, st, off = _run(L, ops, lists, seeds)
-    want = _per_variant(L, ops, lists, seeds)
-    assert rc == 1                                                   # some ops are invalid by construction
-    bad = np.nonzero(st)[0]
-    assert len(bad) >= 5 and all(len(got[i]) == 0 for i in bad)
-    assert all(st[i] == 1 for i in bad)                              # ZkpError::InvalidInput
-    for i in range(len(ops)):
-        assert got[i] == want[i], (i, int(ops["kind"][i]))
-    assert int(off[-1]) == sum(len(p) for p in want)
+    edges, edge_bad = _boundary_batch(12)
+    for (ops, lists, seeds), expect_bad in ((_six_kind_batch(180, 11), None), (edges, edge_bad)):
+        rc, got, st, off = _run(L, ops, lists, seeds)
+        want_st = np.zeros(len(ops), dtype=np.int32)
+        want = _per_variant(L, ops, lists, seeds, want_st)
+        assert rc == 1                                               # some ops are invalid by construction
+        bad = np.nonzero(st)[0]
+        assert len(bad) >= 5 and all(len(got[i]) == 0 for i in bad)
+        assert all(st[i] == 1 for i in bad)                          # ZkpError::InvalidInput
+        assert expect_bad is None or list(bad) == expect_bad
+        assert (st == want_st).all(), (st, want_st)
+        for i in range(len(ops)):
+            assert got[i] == want[i], (i, int(ops["kind"][i]))
+        assert int(off[-1]) == sum(len(p) for p in want)
 
 
 def test_c5_mix_bytes_and_order():
