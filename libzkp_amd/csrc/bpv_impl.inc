@@ -114,6 +114,8 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
         HIP_TRY(hipMemcpyAsync(res, base + o_res, sizeof res, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         accepted_as_a_batch = res[8] == 1;
+        if (!accepted_as_a_batch && getenv("ZKP_HIP_BP_BATCH_VERIFY_ONLY"))                           // diagnostic: the verdict of this check, no per-job pass
+            return fail(ZKP_HIP_E_RUNTIME, "Bulletproofs verification: the batch check did not stand and ZKP_HIP_BP_BATCH_VERIFY_ONLY is set");
         if (accepted_as_a_batch) HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * Mw, st));                // every surviving job's sum is the identity
         else HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));                     // weighted scalars out, per-job path below
     }
