@@ -110,7 +110,20 @@ int zkp_hip_prove_consistency_batch(uint64_t n, const uint64_t* data, const uint
 /* ---- Groth16 / BN254 (equality and set-membership circuits, /root/reference/src/backend/snark.rs) ----
  * kind: 0 = EqualityCircuit ("equality_mimc"), 1 = MembershipCircuit ("membership_mimc", 64 slots).
  * pk = ark-serialize *uncompressed* ProvingKey<Bn254> bytes, i.e. the content of the reference's
- * `{prefix}_pk.bin` key files (snark.rs:31-38,97-112).  Builds the fixed-base tables of every key point on the GPU. */
+ * `{prefix}_pk.bin` key files (snark.rs:31-38,97-112).  Builds the fixed-base tables of every key point on the GPU.
+ * OR pk = ark-serialize uncompressed VerifyingKey<Bn254> bytes, the content of `{prefix}_vk.bin` (snark.rs:72-115; what
+ * zkp_hip_groth16_generate_key returns in vk_out): a VERIFIER-ONLY key.  The proving key file starts with exactly these bytes
+ * (alpha_g1 64 B | beta_g2, gamma_g2, delta_g2 128 B each | u64 count | count x gamma_abc_g1 64 B), so the blob is read as that prefix
+ * first: if it ends exactly behind gamma_abc_g1 it is a verifying key, if bytes remain it is read as a proving key.  A verifying key
+ * loads only what the verifiers read (gamma_abc_g1 and alpha as radix-2^10 window tables, the Miller value of (beta, -alpha), the line
+ * tables of gamma and delta: 3.2 MB for equality, 140 MB for membership, per shard) -- no circuit, no MSM tables.  ZKP_HIP_E_ARGUMENT with a message
+ * naming the verifying key when its gamma_abc_g1 count is not the circuit's instance count, when alpha, beta, gamma, delta or a
+ * gamma_abc_g1 point is the point at infinity, or when the blob is truncated; a failed load leaves no key of that circuit behind.
+ * Either format replaces whatever key the circuit had on every shard: a proving key over a verifying key makes the process a prover, a
+ * verifying key over a proving key releases the shard's reference to the MSM tables (freed with the GPU's last reference).
+ * Under a verifier-only key zkp_hip_verify_equality_batch / _membership_batch work as under the proving key (same kernels, same
+ * verdicts); zkp_hip_prove_equality_batch / _membership_batch and zkp_hip_process_batch / zkp_hip_batch_stage of a batch with an op of
+ * that circuit return ZKP_HIP_E_ARGUMENT ("only a verifying key is loaded for this circuit") before any device work. */
 int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len);
 #define ZKP_HIP_TABLES_BP_GENERATORS 2      /* zkp_hip_groth16_key_info: the Bulletproofs generator tables of the shard */
 /* What the loaded key of `kind` holds on the calling thread's shard: the radix of its fixed-base window tables (2^*wbits; *uneven = 1:
@@ -118,6 +131,9 @@ int zkp_hip_groth16_load_key(int kind, const uint8_t* pk, uint64_t len);
  * the two circuits together; ZKP_HIP_G16_TABLE_BUDGET_MB=<MB per key> opts into larger tables (2^14-uneven, ~72 GB, measured 1.7 %
  * faster on the mixed batch), ZKP_HIP_G16_WBITS=8..15 forces a radix; a device with less free memory gets a smaller radix.  The
  * reference keeps a ProvingKey in host memory (snark.rs:40-56); this is the device-side cost of its replacement.  Any pointer may be NULL.
+ * *table_bytes of a proving key counts its MSM tables only.  A verifier-only key (a VerifyingKey given to zkp_hip_groth16_load_key): 0
+ * returned, *wbits = 10, *uneven = 0, *table_bytes = (count + 1) points x 26 windows x 512 entries x 80 bytes, the gamma_abc_g1 / alpha
+ * tables that are all it holds (equality 3 194 880, membership 139 509 760).
  * kind = ZKP_HIP_TABLES_BP_GENERATORS (2): the Bulletproofs generator tables of the shard (zkp_hip_init): *wbits = 10..16, *uneven = 0,
  * *table_bytes = 130 x windows x 2^(wbits-1) x 128 bytes; *wbits = *table_bytes = 0 (and 0 returned) while ZKP_HIP_ED_TABLES=lazy has
  * not built them yet.  Other kinds: ZKP_HIP_E_ARGUMENT. */
@@ -176,8 +192,8 @@ int zkp_hip_prove_improvement_batch(uint64_t n, const uint64_t* old_values, cons
 int zkp_hip_prove_improvement_batch_device(uint64_t n, const uint64_t* d_old, const uint64_t* d_new, uint8_t* d_out, uint64_t stride,
                                            uint32_t* d_out_len, void* stream);
 
-/* Groth16 verification of equality (scheme 2, 298 B) / membership (scheme 4) envelopes under the verifying key that leads
- * the loaded proving key (zkp_hip_groth16_load_key / _generate_key): SnarkBackend::verify_equality_zk (snark.rs:377-401) and
+/* Groth16 verification of equality (scheme 2, 298 B) / membership (scheme 4) envelopes under the loaded verifying key, or the one
+ * that leads the loaded proving key (zkp_hip_groth16_load_key / _generate_key): SnarkBackend::verify_equality_zk (snark.rs:377-401) and
  * verify_membership_zk (snark.rs:455-495) as reached from verify_proof_cryptographic (proof_helpers.rs:180-206).  The public
  * inputs are the envelope's own commitment (and embedded set); callers compare those with what they expect, as
  * equality_proof.rs:34-60 / set_membership.rs:40-70 do.  ok[i] = 1 accepted / 0 rejected.

@@ -223,7 +223,8 @@ MAX_SET_SIZE = 64
 _key_dir_override = None
 _keys_loaded = {}
 _reinstall = {}            # kind -> key bytes to load again on first use after shutdown()
-_key_blobs = {}            # kind -> proving-key bytes of the loaded key (multi-GPU: rank 0's key is broadcast, sharding.py)
+_key_blobs = {}            # kind -> key bytes of the loaded key (multi-GPU: rank 0's proving key is broadcast, sharding.py)
+_verifier_only = set()     # kinds whose loaded key is a verifying key alone (`{prefix}_vk.bin`): they verify, they cannot prove
 _KEY_PREFIX = {0: "equality_mimc", 1: "membership_mimc"}          # snark.rs:306,327
 _snark_lock = threading.Lock()
 
@@ -246,27 +247,57 @@ def is_snark_setup_initialized():
     return bool(_keys_loaded)
 
 
-def _ensure_key(kind):
+def _vk_prefix_len(blob):
+    """Bytes of the VerifyingKey that leads an ark-serialize uncompressed ProvingKey<Bn254> (and is the whole of a `_vk.bin`):
+    alpha_g1 | beta_g2, gamma_g2, delta_g2 | u64 n | gamma_abc_g1[n]."""
+    return 64 + 3 * 128 + 8 + 64 * int.from_bytes(blob[448:456], "little")
+
+
+def _ensure_key(kind, verifier=False):
     """load_or_generate_setup (snark.rs:122-139): loads `{dir}/{prefix}_pk.bin` (ark-serialize uncompressed
-    ProvingKey<Bn254>, the reference's own key-file format) or runs a fresh setup on the GPU and persists it."""
+    ProvingKey<Bn254>, the reference's own key-file format) or runs a fresh setup on the GPU and persists it.
+    verifier=True (the verify_* paths): a key directory that holds `{prefix}_vk.bin` but no `{prefix}_pk.bin` is a verifier's
+    deployment -- that verifying key is loaded alone (snark.rs:377-401 verifies with the VerifyingKey only) instead of running a
+    fresh setup under which no foreign envelope could verify.  A prove call with such a directory, before or after, needs the proving
+    key file: it raises instead of generating a second setup over the directory's `_vk.bin`."""
     import os
     with _snark_lock:
-        if kind in _keys_loaded:
+        if kind in _keys_loaded and (verifier or kind not in _verifier_only):
             return
         d = _key_dir_override or os.environ.get("LIBZKP_SNARK_KEY_DIR")
         L = _native.lib()
         path = os.path.join(d, _KEY_PREFIX[kind] + "_pk.bin") if d else None
-        if kind in _reinstall:                                      # after shutdown(): the process keeps ONE setup per circuit
+        vk_path = os.path.join(d, _KEY_PREFIX[kind] + "_vk.bin") if d else None
+        # a prove call where this process holds (or held before shutdown()) a verifying key alone: the proving key file, never a second setup
+        upgrade = not verifier and kind in _verifier_only and (kind in _keys_loaded or kind in _reinstall)
+        if upgrade and not (path and os.path.exists(path)):
+            raise ZkpBackendError("Configuration error: only the verifying key of the %s circuit is loaded and there is no proving key (%s) to prove with"
+                                  % (_KEY_PREFIX[kind], path or _KEY_PREFIX[kind] + "_pk.bin: no key directory set"))
+        if kind in _reinstall and not upgrade:                      # after shutdown(): the process keeps ONE setup per circuit
             blob = _reinstall.pop(kind)
             if L.zkp_hip_groth16_load_key(kind, blob, len(blob)) != 0:
                 raise ZkpBackendError("Configuration error: %s" % _native.last_error())
             _key_blobs[kind] = blob
-            path = path or "<reinstalled>"
+            path = "<reinstalled verifying key>" if kind in _verifier_only else path or "<reinstalled>"
         elif path and os.path.exists(path):
             blob = open(path, "rb").read()
             if L.zkp_hip_groth16_load_key(kind, blob, len(blob)) != 0:
                 raise ZkpBackendError("Configuration error: %s" % _native.last_error())
             _key_blobs[kind] = blob
+            _verifier_only.discard(kind)
+            _reinstall.pop(kind, None)
+        elif verifier and vk_path and os.path.exists(vk_path):
+            blob = open(vk_path, "rb").read()
+            if L.zkp_hip_groth16_load_key(kind, blob, len(blob)) != 0:
+                raise ZkpBackendError("Configuration error: %s" % _native.last_error())
+            _key_blobs[kind] = blob
+            _verifier_only.add(kind)
+            path = vk_path
+        elif vk_path and os.path.exists(vk_path):
+            # a prove call in a directory that holds the verifying key but not the proving key: a fresh setup here would overwrite that
+            # `_vk.bin` with the key of another setup, under which nothing proved elsewhere verifies
+            raise ZkpBackendError("Configuration error: %s holds the verifying key of the %s circuit but no proving key (%s) to prove with; "
+                                  "a fresh setup would replace that verifying key" % (d, _KEY_PREFIX[kind], path))
         else:
             # load_or_generate_setup (snark.rs:122-139): fresh trusted setup (OS randomness), persisted if a key dir is set
             pk_len, vk_len = ctypes.c_uint64(), ctypes.c_uint64()
@@ -282,6 +313,7 @@ def _ensure_key(kind):
                 except OSError:
                     pass                                              # the reference ignores persist errors too (snark.rs:131-133)
             _key_blobs[kind] = pk.raw[: pk_len.value]
+            _verifier_only.discard(kind)
             path = path or "<generated in memory>"
         _keys_loaded[kind] = path
 
@@ -312,13 +344,36 @@ def export_proving_key(kind):
     return _key_blobs[kind]
 
 
+def export_verifying_key(kind):
+    """The verifying key of a circuit in ark-serialize uncompressed form (the content of `{prefix}_vk.bin`): the installed verifying
+    key, or the VerifyingKey that leads the loaded (or freshly generated) proving key."""
+    _ensure_key(kind, verifier=True)
+    blob = _key_blobs[kind]
+    return blob[:_vk_prefix_len(blob)]
+
+
 def install_proving_key(kind, blob):
     """Make `blob` THE proving key of this process (every rank of a multi-GPU job must prove under one setup)."""
     with _snark_lock:
         if _native.lib().zkp_hip_groth16_load_key(kind, blob, len(blob)) != 0:
             raise ZkpBackendError("Configuration error: %s" % _native.last_error())
         _key_blobs[kind] = bytes(blob)
+        _verifier_only.discard(kind)
         _keys_loaded[kind] = "<installed>"
+
+
+def install_verifying_key(kind, blob):
+    """Make `blob` (ark-serialize uncompressed VerifyingKey<Bn254>, a `{prefix}_vk.bin`) the key of this process for verification only:
+    no circuit, no MSM tables -- what a verifier service holds.  Replaces a proving key loaded earlier (its tables are freed)."""
+    blob = bytes(blob)
+    if len(blob) < 456 or len(blob) != _vk_prefix_len(blob):
+        raise ZkpBackendError("Configuration error: not a verifying key (a proving key is installed with install_proving_key)")
+    with _snark_lock:
+        if _native.lib().zkp_hip_groth16_load_key(kind, blob, len(blob)) != 0:
+            raise ZkpBackendError("Configuration error: %s" % _native.last_error())
+        _key_blobs[kind] = blob
+        _verifier_only.add(kind)
+        _keys_loaded[kind] = "<installed verifying key>"
 
 
 def snark_commit_value_batch(values):
@@ -467,7 +522,7 @@ def _verify_snark_envelopes(kind, blobs):
     n = len(blobs)
     if n == 0:
         return []
-    _ensure_key(kind)
+    _ensure_key(kind, verifier=True)
     buf, lens, stride = _rows(blobs, 4096)
     ok = np.zeros(n, dtype=np.uint8)
     fn = _native.lib().zkp_hip_verify_equality_batch if kind == 0 else _native.lib().zkp_hip_verify_membership_batch

@@ -268,6 +268,9 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
             default: P.n_con++; if (consistency_envelope_bytes(o.count ? o.count : 1) > P.stride_con) P.stride_con = consistency_envelope_bytes(o.count ? o.count : 1); break;
         }
     }
+    // a shard that holds only a verifying key for a circuit cannot prove its ops: said here, before anything is allocated or uploaded
+    if (P.n_eq && g16s().key[G16_EQUALITY].verifier_only()) return no_proving_key(g16s().key[G16_EQUALITY]);
+    if (P.n_mem && g16s().key[G16_MEMBERSHIP].verifier_only()) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
     // the generator tables are built here, not at launch, when ZKP_HIP_ED_TABLES=lazy left them for the first batch that needs them
     if ((P.n_range || P.n_thr || P.n_con) && (rc = ensure_bp())) return rc;
     // ---- layout of the staging image, the arena and the result block
@@ -459,8 +462,8 @@ int launch_shard_enqueue(ShardPlan& P) {
 int launch_shard(ShardPlan& P) {
     if (P.generation != dev().generation) return fail(ZKP_HIP_E_ARGUMENT, "the batch was staged before zkp_hip_shutdown: stage it again");
     // nothing is enqueued unless every key the batch needs is there (a later variant failing would leave the earlier chains running)
-    if ((P.n_eq && !g16s().key[G16_EQUALITY].loaded) || (P.n_mem && !g16s().key[G16_MEMBERSHIP].loaded))
-        return fail(ZKP_HIP_E_ARGUMENT, "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
+    if (P.n_eq && !g16s().key[G16_EQUALITY].loaded) return no_proving_key(g16s().key[G16_EQUALITY]);
+    if (P.n_mem && !g16s().key[G16_MEMBERSHIP].loaded) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
     const int rc = launch_shard_enqueue(P);
     if (rc) {                                     // part of the batch may be running on the lane's streams: the caller is about to hand
         const std::string keep = t_err;           // the shard's blocks back to the pool, so nothing may still be writing them

@@ -6,7 +6,7 @@ namespace {
 
 // ---- device-resident key + circuit
 struct G16Key {
-    bool loaded = false;
+    bool loaded = false;                                // a PROVING key is loaded (circuit, MSM tables, layouts); a verifier-only key has vk_ready alone
     uint32_t n_inst = 0, n_wit = 0, nv = 0, n_rows = 0, m = 0, logm = 0;
     G16Circuit C{};
     std::vector<void*> allocs;
@@ -21,7 +21,9 @@ struct G16Key {
     std::map<uint64_t, Chunking> lays_g1, lays_g2;            // key = part << 32 | chunk count
     uint64_t win_g1 = 0, win_g2 = 0;          // windows (= mixed additions) per proof
     const uint32_t *init_g1 = nullptr, *init_g2 = nullptr;
-    G16Vk vk{}; bool vk_ready = false;        // the verifying key that leads the proving key file (verification entry points)
+    G16Vk vk{}; bool vk_ready = false;        // the verifying key (loaded alone, or the one that leads the proving key file): all the verification entry points read
+    uint64_t vk_table_bytes = 0;              // HBM held by vk.ic_table
+    bool verifier_only() const { return vk_ready && !loaded; }
     const uint32_t *vm_kconst = nullptr, *vm_lines = nullptr;      // the Fq2 machine's Miller value of (beta, -alpha) and line table of gamma, delta (fq2vm.h)
 };
 // per-shard Groth16 state (Device::g16): both circuits' keys, the MiMC constants, one workspace + side stream per circuit
@@ -156,53 +158,7 @@ int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chun
     return 0;
 }
 
-// ---- ark-serialize (uncompressed) proving key
-struct KeyReader {
-    const uint8_t* p; uint64_t left; bool ok = true;
-    const uint8_t* take(uint64_t n) { if (left < n) { ok = false; return nullptr; } const uint8_t* q = p; p += n; left -= n; return q; }
-    uint64_t u64() { const uint8_t* q = take(8); uint64_t v = 0; if (q) for (int i = 0; i < 8; i++) v |= (uint64_t)q[i] << (8 * i); return v; }
-};
-// canonical-encoding check on the serialized words
-bool raw_lt_p(const uint32_t w[8]) { for (int i = 7; i >= 0; i--) { if (w[i] < FqParams::mod(i)) return true; if (w[i] > FqParams::mod(i)) return false; } return false; }
-// returns 0 ok (inf set if point at infinity), -1 malformed
-int parse_g1(KeyReader& R, bool& inf, g1_aff& out) {
-    const uint8_t* q = R.take(64); if (!q) return -1;
-    uint8_t buf[64]; memcpy(buf, q, 64);
-    const uint8_t flags = buf[63] & 0xC0; buf[63] &= 0x3F;
-    if (flags == 0xC0) return -1;                        // SWFlags::from_u8 rejects both bits set
-    inf = flags & 0x40; if (inf) return 0;
-    uint32_t w[16]; memcpy(w, buf, 64);
-    if (!raw_lt_p(w) || !raw_lt_p(w + 8)) return -1;
-    out.x = fq_from_raw(w); out.y = fq_from_raw(w + 8);
-    const fq rhs = fq_add(fq_mul(fq_sq(out.x), out.x), fq_from_u64(3));
-    return fq_eq(fq_sq(out.y), rhs) ? 0 : -1;
-}
-int parse_g2(KeyReader& R, bool& inf, g2_aff& out) {
-    const uint8_t* q = R.take(128); if (!q) return -1;
-    uint8_t buf[128]; memcpy(buf, q, 128);
-    const uint8_t flags = buf[127] & 0xC0; buf[127] &= 0x3F;
-    if (flags == 0xC0) return -1;
-    inf = flags & 0x40; if (inf) return 0;
-    uint32_t w[32]; memcpy(w, buf, 128);
-    for (int k = 0; k < 4; k++) if (!raw_lt_p(w + 8 * k)) return -1;
-    out.x = fq2{fq_from_raw(w), fq_from_raw(w + 8)}; out.y = fq2{fq_from_raw(w + 16), fq_from_raw(w + 24)};
-    const fq2 b2 = f_mul(fq2{fq_from_u64(3), fq_zero()}, f_inv(fq2{fq_from_u64(9), fq_from_u64(1)}));
-    const fq2 lhs = f_sq(out.y), rhs = f_add(f_mul(f_sq(out.x), out.x), b2);
-    return (fq_eq(lhs.c0, rhs.c0) && fq_eq(lhs.c1, rhs.c1)) ? 0 : -1;
-}
-struct G1Pt { bool inf; g1_aff p; };
-struct G2Pt { bool inf; g2_aff p; };
-int parse_vec_g1(KeyReader& R, std::vector<G1Pt>& v) {
-    const uint64_t n = R.u64(); if (!R.ok || n > (1u << 24)) return -1;
-    v.resize(n); for (auto& e : v) if (parse_g1(R, e.inf, e.p)) return -1;
-    return 0;
-}
-int parse_vec_g2(KeyReader& R, std::vector<G2Pt>& v) {
-    const uint64_t n = R.u64(); if (!R.ok || n > (1u << 24)) return -1;
-    v.resize(n); for (auto& e : v) if (parse_g2(R, e.inf, e.p)) return -1;
-    return 0;
-}
-
+// ---- ark-serialize (uncompressed) proving / verifying key: the point reader and the format rule are in g16_keyblob.h
 
 // ---- key tables: sized at run time, shared by the shards of one physical GPU
 // bytes of the two MSM tables of a key with n1 G1 and n2 G2 points at radix 2^wbits
@@ -286,6 +242,11 @@ void release_key(G16Key& K) {
     K = G16Key();
 }
 int load_key_body(int kind, const uint8_t* pk, uint64_t len);
+// what a prove call answers when its circuit has no proving key on this shard
+int no_proving_key(const G16Key& K) {
+    return fail(ZKP_HIP_E_ARGUMENT, K.verifier_only() ? "only a verifying key is loaded for this circuit: proving needs the proving key (zkp_hip_groth16_load_key)"
+                                                      : "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
+}
 int load_key_locked(int kind, const uint8_t* pk, uint64_t len) {
     if (kind != G16_EQUALITY && kind != G16_MEMBERSHIP) return fail(ZKP_HIP_E_ARGUMENT, "unknown circuit kind");
     G16Key& K = g16s().key[kind];
@@ -296,22 +257,59 @@ int load_key_locked(int kind, const uint8_t* pk, uint64_t len) {
     if (rc) { const std::string keep = t_err; release_key(K); t_err = keep; }      // a failed load leaves no table reference and no allocation behind
     return rc;
 }
+// The verifying-key part of a key, shared by both formats: gamma, delta, gamma_abc_g1 and the constant Miller-loop factor of
+// (beta, -alpha), computed once on the host.  Nothing else is needed to verify (g16_verify.h, fq2vm.h, g16_rlc.h).
+int install_verifying_key(G16Key& K, const G16VkBlob& B) {
+    int rc;
+    K.vk_ready = false;
+    std::vector<uint32_t> icw; for (auto& e : B.abc) append_words(icw, e.p);
+    append_words(icw, B.alpha_g1.p);                 // point n_ic of the verifier's tables: alpha (the batch check's virtual envelope, g16_rlc.h)
+    const uint32_t* d_ic = nullptr;
+    if ((rc = dev_upload(K, &d_ic, icw))) return rc;
+    // gamma_abc_g1 are fixed points of the key: the verifier's public-input accumulation walks radix-1024 window tables
+    // (the prover's table builder) instead of doubling-and-adding
+    std::vector<g1_aff> ic_pts; for (auto& e : B.abc) ic_pts.push_back(e.p);
+    ic_pts.push_back(B.alpha_g1.p);
+    uint32_t* d_ic_tab = nullptr;
+    const G16Radix vrx = g16_radix(G16V_WBITS);
+    if ((rc = build_tables<20>(K, ic_pts, &d_ic_tab, false, vrx))) return rc;
+    K.vk_table_bytes = (uint64_t)ic_pts.size() * vrx.slot_ent * g16_table_entry_words(false, false) * 4ull;
+    K.vk.gamma = B.gamma_g2.p; K.vk.delta = B.delta_g2.p; K.vk.beta = B.beta_g2.p; K.vk.n_ic = (uint32_t)B.abc.size(); K.vk.ic = d_ic; K.vk.ic_table = d_ic_tab;
+    K.vk.ml_alpha_beta = miller_loop(B.beta_g2.p, aff_neg(B.alpha_g1.p));
+    std::vector<uint32_t> kc(6 * 20), lines;
+    g16_vm_key_constants(B.beta_g2.p, aff_neg(B.alpha_g1.p), B.gamma_g2.p, B.delta_g2.p, kc.data(), lines);
+    if ((rc = dev_upload(K, &K.vm_kconst, kc)) || (rc = dev_upload(K, &K.vm_lines, lines))) return rc;
+    K.vk_ready = true;
+    return 0;
+}
+int ensure_mimc_dev() {
+    if (g16s().mimc_dev) return 0;
+    ensure_mimc_constants();
+    std::vector<uint32_t> mc; for (auto& c : g_mimc_host) put_fr(mc, c);
+    HIP_TRY(hipMalloc(&g16s().mimc_dev, mc.size() * 4)); HIP_TRY(hipMemcpy(g16s().mimc_dev, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
 int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     G16Key& K = g16s().key[kind];
     const HostR1CS cs = kind == G16_EQUALITY ? build_equality_r1cs() : build_membership_r1cs();
     int rc;
-    if ((rc = upload_circuit(K, cs))) return rc;
-    if (!g16s().mimc_dev) {
-        ensure_mimc_constants();
-        std::vector<uint32_t> mc; for (auto& c : g_mimc_host) put_fr(mc, c);
-        HIP_TRY(hipMalloc(&g16s().mimc_dev, mc.size() * 4)); HIP_TRY(hipMemcpy(g16s().mimc_dev, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
-    }
-    // ProvingKey { vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query }
+    // ProvingKey { vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query },
+    // or its vk alone: a blob that ends behind gamma_abc_g1 is a verifying key (g16_keyblob.h)
     KeyReader R{pk, len};
-    G1Pt alpha_g1, beta_g1, delta_g1; G2Pt beta_g2, gamma_g2, delta_g2;
-    std::vector<G1Pt> abc, aq, b1q, hq, lq; std::vector<G2Pt> b2q;
-    if (parse_g1(R, alpha_g1.inf, alpha_g1.p) || parse_g2(R, beta_g2.inf, beta_g2.p) || parse_g2(R, gamma_g2.inf, gamma_g2.p) ||
-        parse_g2(R, delta_g2.inf, delta_g2.p) || parse_vec_g1(R, abc) || parse_g1(R, beta_g1.inf, beta_g1.p) || parse_g1(R, delta_g1.inf, delta_g1.p) ||
+    G16VkBlob B;
+    const int format = g16_read_key_prefix(R, B);
+    if (format == G16_BLOB_MALFORMED)
+        return fail(ZKP_HIP_E_ARGUMENT, "malformed proving key or verifying key (expected ark-serialize uncompressed ProvingKey<Bn254>, or its VerifyingKey<Bn254> alone)");
+    if (format == G16_BLOB_VERIFYING_KEY) {          // a verifier-only key: no circuit, no MiMC constants, no MSM tables, no registry entry, no layouts
+        if (const char* why = g16_check_verifying_key(B, cs.n_inst)) return fail(ZKP_HIP_E_ARGUMENT, why);
+        return install_verifying_key(K, B);
+    }
+    if ((rc = upload_circuit(K, cs)) || (rc = ensure_mimc_dev())) return rc;
+    const G1Pt &alpha_g1 = B.alpha_g1; const G2Pt &beta_g2 = B.beta_g2, &delta_g2 = B.delta_g2;
+    const std::vector<G1Pt>& abc = B.abc;
+    G1Pt beta_g1, delta_g1;
+    std::vector<G1Pt> aq, b1q, hq, lq; std::vector<G2Pt> b2q;
+    if (parse_g1(R, beta_g1.inf, beta_g1.p) || parse_g1(R, delta_g1.inf, delta_g1.p) ||
         parse_vec_g1(R, aq) || parse_vec_g1(R, b1q) || parse_vec_g2(R, b2q) || parse_vec_g1(R, hq) || parse_vec_g1(R, lq) || !R.ok || R.left != 0)
         return fail(ZKP_HIP_E_ARGUMENT, "malformed proving key (expected ark-serialize uncompressed ProvingKey<Bn254>)");
     if (aq.size() != K.nv || b1q.size() != K.nv || b2q.size() != K.nv || hq.size() != K.m - 1 || lq.size() != K.n_wit || abc.size() != K.n_inst)
@@ -399,29 +397,9 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         K.shared_tables = found; K.table_g1 = R.v[(size_t)found].g1; K.table_g2 = R.v[(size_t)found].g2;
     }
     K.table_bytes = key_table_bytes(bases1.size(), bases2.size(), K.rx.wbits, K.rx.uneven);
-    // verifying key: gamma, delta, gamma_abc_g1 and the constant Miller-loop factor of (beta, -alpha), computed once on the host
+    // the verifying key that leads the file; one that cannot verify (gamma or a gamma_abc_g1 point at infinity) leaves a key that only proves
     K.vk_ready = false;
-    if (!gamma_g2.inf) {
-        bool ic_ok = true; for (auto& e : abc) ic_ok = ic_ok && !e.inf;
-        if (ic_ok) {
-            std::vector<uint32_t> icw; for (auto& e : abc) append_words(icw, e.p);
-            append_words(icw, alpha_g1.p);                 // point n_ic of the verifier's tables: alpha (the batch check's virtual envelope, g16_rlc.h)
-            const uint32_t* d_ic = nullptr;
-            if ((rc = dev_upload(K, &d_ic, icw))) return rc;
-            // gamma_abc_g1 are fixed points of the key: the verifier's public-input accumulation walks radix-1024 window tables
-            // (the prover's table builder) instead of doubling-and-adding
-            std::vector<g1_aff> ic_pts; for (auto& e : abc) ic_pts.push_back(e.p);
-            ic_pts.push_back(alpha_g1.p);
-            uint32_t* d_ic_tab = nullptr;
-            if ((rc = build_tables<20>(K, ic_pts, &d_ic_tab, false, g16_radix(G16V_WBITS)))) return rc;
-            K.vk.gamma = gamma_g2.p; K.vk.delta = delta_g2.p; K.vk.beta = beta_g2.p; K.vk.n_ic = (uint32_t)abc.size(); K.vk.ic = d_ic; K.vk.ic_table = d_ic_tab;
-            K.vk.ml_alpha_beta = miller_loop(beta_g2.p, aff_neg(alpha_g1.p));
-            std::vector<uint32_t> kc(6 * 20), lines;
-            g16_vm_key_constants(beta_g2.p, aff_neg(alpha_g1.p), gamma_g2.p, delta_g2.p, kc.data(), lines);
-            if ((rc = dev_upload(K, &K.vm_kconst, kc)) || (rc = dev_upload(K, &K.vm_lines, lines))) return rc;
-            K.vk_ready = true;
-        }
-    }
+    if (!g16_check_verifying_key(B, K.n_inst) && (rc = install_verifying_key(K, B))) return rc;
     K.loaded = true;
     return 0;
 }
@@ -559,7 +537,7 @@ int launch_msm_key(bool g2, const G16Radix& rx, const G16Key::Chunking& ch, cons
 int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_set_vals, const uint32_t* d_set_len, const uint8_t* d_seeds,
             uint8_t* d_out, uint64_t stride, hipStream_t st, uint32_t lane = 0) {
     G16Key& K = g16s().key[kind];
-    if (!K.loaded) return fail(ZKP_HIP_E_ARGUMENT, "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
+    if (!K.loaded) return no_proving_key(K);
     const uint32_t nsc = g16_nscalars(K.nv, K.m);
     // The steps of one batch in dependency order on three streams, so that the latency-bound ones
     // (QAP, partial sums, the two scalar multiplications) sit beside an MSM instead of between two:
@@ -642,6 +620,7 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
 // host-buffer front end shared by equality and membership: validates, compacts the valid ops, runs, scatters
 int prove_g16_host(int kind, uint64_t n, const uint64_t* values, const uint64_t* sets_flat, const uint32_t* set_counts, const std::vector<uint8_t>& valid,
                    const uint8_t* seeds, uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status) {
+    if (g16s().key[kind].verifier_only()) return no_proving_key(g16s().key[kind]);          // before anything is written or enqueued
     std::vector<uint64_t> v, sv; std::vector<uint32_t> sl, idx; std::vector<uint8_t> sd;
     size_t pos = 0; int any = 0;
     memset(out, 0, stride * n);
@@ -708,7 +687,7 @@ void g16_release_all() {
 // handle those cases.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test knob) takes the lane-per-chain kernels for everything.
 int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
     G16Key& K = g16s().key[kind];
-    if (!K.loaded || !K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
+    if (!K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
     hipStream_t st = dev().stream;
     uint8_t *d_in = nullptr, *d_ok = nullptr, *d_scratch = nullptr; uint32_t *d_len = nullptr, *d_special = nullptr;
     DevScope mem;
@@ -805,6 +784,12 @@ int zkp_hip_groth16_key_info(int kind, uint32_t* wbits, uint32_t* uneven, uint64
         return 0;
     }
     const G16Key& K = g16s().key[kind];
+    if (K.verifier_only()) {          // no MSM tables: the gamma_abc_g1 window tables are all the key holds
+        if (wbits) *wbits = G16V_WBITS;
+        if (uneven) *uneven = 0;
+        if (table_bytes) *table_bytes = K.vk_table_bytes;
+        return 0;
+    }
     if (!K.loaded) return fail(ZKP_HIP_E_ARGUMENT, "no proving key loaded for this circuit (zkp_hip_groth16_load_key)");
     if (wbits) *wbits = K.rx.wbits;
     if (uneven) *uneven = K.rx.uneven ? 1u : 0u;
@@ -848,11 +833,7 @@ int zkp_hip_snark_commit_value_batch(uint64_t n, const uint64_t* values, uint8_t
     if (n == 0) return 0;
     Bind bind; int rc = host_args(n, {values, out});
     if (rc || (rc = bind.open())) return rc;
-    if (!g16s().mimc_dev) {
-        ensure_mimc_constants();
-        std::vector<uint32_t> mc; for (auto& c : g_mimc_host) put_fr(mc, c);
-        HIP_TRY(hipMalloc(&g16s().mimc_dev, mc.size() * 4)); HIP_TRY(hipMemcpy(g16s().mimc_dev, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
-    }
+    if ((rc = ensure_mimc_dev())) return rc;
     uint64_t* d_v = nullptr; uint8_t* d_o = nullptr;
     DevScope mem;
     HIP_TRY(mem.alloc(&d_v, 8 * n)); HIP_TRY(mem.alloc(&d_o, 32 * n));

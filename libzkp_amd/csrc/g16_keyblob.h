@@ -1,0 +1,81 @@
+// Groth16 key blobs (host only): the ark-serialize uncompressed point reader of the key loader, and the rule that tells the two
+// formats zkp_hip_groth16_load_key accepts apart.  ProvingKey<Bn254> starts with its VerifyingKey<Bn254>
+//   { alpha_g1 (64 B), beta_g2, gamma_g2, delta_g2 (128 B each), u64 count, count x gamma_abc_g1 (64 B each) }
+// so a blob is read as that prefix first: if it ENDS exactly there it is a verifying key, if bytes remain it is a proving key and the
+// reader goes on from where the prefix ended.  No length table and no flag.  Compiled for the host by tests/emul/emul_g16_keyblob.cpp too.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "bn254_g.h"
+
+namespace zkp {
+
+struct KeyReader {
+    const uint8_t* p; uint64_t left; bool ok = true;
+    const uint8_t* take(uint64_t n) { if (left < n) { ok = false; return nullptr; } const uint8_t* q = p; p += n; left -= n; return q; }
+    uint64_t u64() { const uint8_t* q = take(8); uint64_t v = 0; if (q) for (int i = 0; i < 8; i++) v |= (uint64_t)q[i] << (8 * i); return v; }
+};
+// canonical-encoding check on the serialized words
+inline bool raw_lt_p(const uint32_t w[8]) { for (int i = 7; i >= 0; i--) { if (w[i] < FqParams::mod(i)) return true; if (w[i] > FqParams::mod(i)) return false; } return false; }
+// returns 0 ok (inf set if point at infinity), -1 malformed
+inline int parse_g1(KeyReader& R, bool& inf, g1_aff& out) {
+    const uint8_t* q = R.take(64); if (!q) return -1;
+    uint8_t buf[64]; memcpy(buf, q, 64);
+    const uint8_t flags = buf[63] & 0xC0; buf[63] &= 0x3F;
+    if (flags == 0xC0) return -1;                        // SWFlags::from_u8 rejects both bits set
+    inf = flags & 0x40; if (inf) return 0;
+    uint32_t w[16]; memcpy(w, buf, 64);
+    if (!raw_lt_p(w) || !raw_lt_p(w + 8)) return -1;
+    out.x = fq_from_raw(w); out.y = fq_from_raw(w + 8);
+    const fq rhs = fq_add(fq_mul(fq_sq(out.x), out.x), fq_from_u64(3));
+    return fq_eq(fq_sq(out.y), rhs) ? 0 : -1;
+}
+inline int parse_g2(KeyReader& R, bool& inf, g2_aff& out) {
+    const uint8_t* q = R.take(128); if (!q) return -1;
+    uint8_t buf[128]; memcpy(buf, q, 128);
+    const uint8_t flags = buf[127] & 0xC0; buf[127] &= 0x3F;
+    if (flags == 0xC0) return -1;
+    inf = flags & 0x40; if (inf) return 0;
+    uint32_t w[32]; memcpy(w, buf, 128);
+    for (int k = 0; k < 4; k++) if (!raw_lt_p(w + 8 * k)) return -1;
+    out.x = fq2{fq_from_raw(w), fq_from_raw(w + 8)}; out.y = fq2{fq_from_raw(w + 16), fq_from_raw(w + 24)};
+    const fq2 b2 = f_mul(fq2{fq_from_u64(3), fq_zero()}, f_inv(fq2{fq_from_u64(9), fq_from_u64(1)}));
+    const fq2 lhs = f_sq(out.y), rhs = f_add(f_mul(f_sq(out.x), out.x), b2);
+    return (fq_eq(lhs.c0, rhs.c0) && fq_eq(lhs.c1, rhs.c1)) ? 0 : -1;
+}
+struct G1Pt { bool inf; g1_aff p; };
+struct G2Pt { bool inf; g2_aff p; };
+inline int parse_vec_g1(KeyReader& R, std::vector<G1Pt>& v) {
+    const uint64_t n = R.u64(); if (!R.ok || n > (1u << 24)) return -1;
+    v.resize(n); for (auto& e : v) if (parse_g1(R, e.inf, e.p)) return -1;
+    return 0;
+}
+inline int parse_vec_g2(KeyReader& R, std::vector<G2Pt>& v) {
+    const uint64_t n = R.u64(); if (!R.ok || n > (1u << 24)) return -1;
+    v.resize(n); for (auto& e : v) if (parse_g2(R, e.inf, e.p)) return -1;
+    return 0;
+}
+
+// VerifyingKey { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }: alone, or as the head of a proving key
+struct G16VkBlob { G1Pt alpha_g1{}; G2Pt beta_g2{}, gamma_g2{}, delta_g2{}; std::vector<G1Pt> abc; };
+enum { G16_BLOB_MALFORMED = -1, G16_BLOB_PROVING_KEY = 0, G16_BLOB_VERIFYING_KEY = 1 };
+// Reads the prefix and classifies the blob; R is left behind gamma_abc_g1 (a proving key's beta_g1 comes next).  MALFORMED: the prefix
+// itself is truncated or holds a word that is no field element / a point off the curve.  Points at infinity are valid encodings here:
+// what each format makes of them is its loader's business (g16_check_verifying_key for a verifying key).
+inline int g16_read_key_prefix(KeyReader& R, G16VkBlob& vk) {
+    if (parse_g1(R, vk.alpha_g1.inf, vk.alpha_g1.p) || parse_g2(R, vk.beta_g2.inf, vk.beta_g2.p) || parse_g2(R, vk.gamma_g2.inf, vk.gamma_g2.p) ||
+        parse_g2(R, vk.delta_g2.inf, vk.delta_g2.p) || parse_vec_g1(R, vk.abc) || !R.ok) return G16_BLOB_MALFORMED;
+    return R.left == 0 ? G16_BLOB_VERIFYING_KEY : G16_BLOB_PROVING_KEY;
+}
+inline uint64_t g16_vk_blob_bytes(uint64_t n_ic) { return 64 + 3 * 128 + 8 + 64 * n_ic; }
+// what a verifying key must satisfy to be usable for the circuit with n_inst instance variables (the constant one included): the message
+// of the first rule it breaks, or nullptr
+inline const char* g16_check_verifying_key(const G16VkBlob& vk, uint32_t n_inst) {
+    if (vk.abc.size() != n_inst) return "verifying key does not match the circuit shape (gamma_abc_g1 count)";
+    if (vk.alpha_g1.inf || vk.beta_g2.inf || vk.gamma_g2.inf || vk.delta_g2.inf) return "degenerate verifying key (alpha, beta, gamma or delta at infinity)";
+    for (const auto& e : vk.abc) if (e.inf) return "degenerate verifying key (a gamma_abc_g1 point at infinity)";
+    return nullptr;
+}
+
+}  // namespace zkp

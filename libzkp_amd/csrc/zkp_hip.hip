@@ -27,6 +27,7 @@
 #include "g16_steps.h"
 #include "sha256_host.h"
 #include "g16_circuit.h"
+#include "g16_keyblob.h"
 #include "msm_kernel.h"
 #include "g16_launch.h"
 #include "g16_verify_launch.h"

@@ -51,16 +51,18 @@ def process_range_batch_sharded(values, mins, maxs, seeds, prover=None, device=N
     return out
 
 
-def share_snark_keys(kinds, device=None, export=None, install=None):
-    """One trusted setup for the whole job: rank 0 loads or generates the proving key of each circuit in
+def share_snark_keys(kinds, device=None, export=None, install=None, verifier=False):
+    """One trusted setup for the whole job: rank 0 loads or generates the key of each circuit in
     `kinds` (0 equality, 1 membership) and broadcasts its ark-serialized bytes; the other ranks install exactly that key.
-    Without this every rank would run its own random setup and the job's proofs would verify under different keys."""
+    Without this every rank would run its own random setup and the job's proofs would verify under different keys.
+    The key is the proving key, or with verifier=True the verifying key alone (a job whose ranks only verify: rank 0 needs
+    no more than a `{prefix}_vk.bin`, and no rank builds MSM tables)."""
     import torch
     import torch.distributed as dist
 
     from . import api
-    export = export or api.export_proving_key
-    install = install or api.install_proving_key
+    export = export or (api.export_verifying_key if verifier else api.export_proving_key)
+    install = install or (api.install_verifying_key if verifier else api.install_proving_key)
     if not dist.is_initialized() or dist.get_world_size() == 1:
         for k in kinds:
             export(k)

@@ -153,6 +153,25 @@ pub fn load_proving_key(kind: i32, pk_bytes: &[u8]) -> ZkpResult<()> {
     Ok(())
 }
 
+/// A verifier's process (snark.rs:377-401, 455-495 verify with the `VerifyingKey` alone): hand the reference's `{prefix}_vk.bin` bytes
+/// (ark-serialize uncompressed `VerifyingKey<Bn254>`) to every GPU.  Same entry point as `load_proving_key` -- the library tells the two
+/// formats apart by whether the blob ends behind `gamma_abc_g1` -- but nothing except the verifier's tables is built (3.2 MB / 140 MB of
+/// device memory instead of the proving key's gigabytes), and the prove calls of that circuit then fail with `ConfigError`.
+pub fn load_verifying_key(kind: i32, vk_bytes: &[u8]) -> ZkpResult<()> {
+    if vk_bytes.len() < 456 {
+        return Err(ZkpError::ConfigError("verifying key too short".into()));
+    }
+    let n_ic = u64::from_le_bytes(vk_bytes[448..456].try_into().unwrap());
+    if n_ic > (1 << 24) || vk_bytes.len() as u64 != 456 + 64 * n_ic {
+        return Err(ZkpError::ConfigError("not a verifying key (a proving key goes through load_proving_key)".into()));
+    }
+    let rc = unsafe { ffi::zkp_hip_groth16_load_key(kind, vk_bytes.as_ptr(), vk_bytes.len() as u64) };
+    if rc != 0 {
+        return Err(ZkpError::ConfigError(ffi::last_error()));
+    }
+    Ok(())
+}
+
 /// `zkp_hip_groth16_key_info` kind of the Bulletproofs generator tables (`ZKP_HIP_TABLES_BP_GENERATORS`, include/libzkp_hip.h).
 pub const ZKP_HIP_TABLES_BP_GENERATORS: i32 = 2;
 
