@@ -199,7 +199,15 @@ int zkp_hip_prove_improvement_batch_device(uint64_t n, const uint64_t* d_old, co
  * equality_proof.rs:34-60 / set_membership.rs:40-70 do.  ok[i] = 1 accepted / 0 rejected.
  * Calls with more than 8192 envelopes first try ONE weighted pairing check for all of them (fresh 128-bit weights from getrandom;
  * libzkp_amd/csrc/g16_rlc.h) and verify envelope by envelope only if it does not stand, so every verdict is the per-envelope one up to a
- * soundness error of 2^-128 per call; ZKP_HIP_NO_BATCH_VERIFY=1 / ZKP_HIP_G16_BATCH_VERIFY_MIN move or remove the threshold. */
+ * soundness error of 2^-128 per call; ZKP_HIP_NO_BATCH_VERIFY=1 / ZKP_HIP_G16_BATCH_VERIFY_MIN move or remove the threshold.
+ * When that check does not stand, the call cuts the batch into contiguous segments, checks every segment the same way from what the first check
+ * left on the device (same weights; soundness error at most (1 + segments) 2^-128 per call, at most 8192 segments) and gives only the envelopes
+ * of suspect segments -- a product that is not one, a point at infinity, a B outside G2 -- the per-envelope check, so one bad envelope costs a
+ * segment, not the batch.  Suspects in half of the batch or more: the whole batch is verified envelope by envelope.  Read on every call:
+ * ZKP_HIP_G16_LOCALISE=0 goes straight to the whole per-envelope pass, ZKP_HIP_G16_LOCALISE_SEGMENT=<envelopes> sets the segment size (default:
+ * about n / 256, at least 64), ZKP_HIP_G16_BATCH_VERIFY_ONLY=1 (diagnostic) makes a call whose batch check does not stand fail with
+ * ZKP_HIP_E_RUNTIME ("the batch check did not stand") instead.  What the calls did after failed checks is counted per shard:
+ * zkp_hip_profile_read_kernel(ZKP_HIP_COUNTER_G16_VERIFY, ...). */
 int zkp_hip_verify_equality_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok);
 int zkp_hip_verify_membership_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok);
 
@@ -270,7 +278,12 @@ void zkp_hip_batch_free(zkp_hip_batch* batch);
 void zkp_hip_profile_enable(int on);
 /* Synchronises, then returns accumulated MSM kernel time (ms), launch count, and table-entry gathers
  * (point additions) since the last reset, summed over the shards.  zkp_hip_profile_read is kernel 0. */
-enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_KERNEL_MSM_BN254_G2 = 2 };
+enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_KERNEL_MSM_BN254_G2 = 2,
+       /* Not a kernel: what zkp_hip_verify_equality_batch / _membership_batch did after batch checks that did not stand.  Always counted (no
+        * zkp_hip_profile_enable needed), summed over the shards, same `reset`.  *launches = segment checks run (virtual envelopes sent through the
+        * pairing chains by localisation passes); *point_adds = envelopes given the per-envelope check after a failed batch check (the compacted
+        * suspects, or n when the whole batch was verified again); *ms = host wall time from the failed check's verdict to the call's return. */
+       ZKP_HIP_COUNTER_G16_VERIFY = 3 };
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset);
 int zkp_hip_profile_read(double* msm_ms, uint64_t* msm_launches, uint64_t* msm_point_adds, int reset);
 /* Tunable (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ZKP_HIP_LIB") or os.path.join(_HERE, "lib", "libzkp_h
 
 RANGE_PROOF_BYTES = 1478
 TABLES_BP_GENERATORS = 2          # zkp_hip_groth16_key_info kind: the Bulletproofs generator tables (include/libzkp_hip.h)
+COUNTER_G16_VERIFY = 3            # zkp_hip_profile_read_kernel id: what the Groth16 verifier did after failed batch checks (include/libzkp_hip.h)
 # symbols declared in include/libzkp_hip.h (checked by tests/test_abi.py)
 EXPORTS = (
     "zkp_hip_init", "zkp_hip_shutdown", "zkp_hip_last_error", "zkp_hip_prove_range_batch",

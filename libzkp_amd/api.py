@@ -530,6 +530,17 @@ def _verify_snark_envelopes(kind, blobs):
     return ok.astype(bool).tolist()
 
 
+def groth16_verify_counters(reset=True):
+    """What verify_equality_batch / verify_membership_batch did after batch checks that did not stand, summed over the shards since the last
+    reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_G16_VERIFY; always counted): {"launches": segment checks run by localisation
+    passes, "point_adds": envelopes given the per-envelope check after a failed batch check (the suspects, or the whole batch), "ms": host
+    wall time from the failed checks' verdicts to the calls' returns}.  reset=True zeroes the counters."""
+    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_G16_VERIFY, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
+                  "zkp_hip_profile_read_kernel")
+    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+
+
 def verify_equality_with_commitment_batch(proofs, commitments):
     """Batched verify_equality_with_commitment (equality_proof.rs:34-60): the envelope must carry exactly that commitment."""
     blobs = [bytes(p) for p in proofs]

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "g16_rlc.h"
+#include "g16_localise.h"
 #include "fq2vm.h"
 #include "g16_verify_launch.h"
 using namespace zkp;
@@ -451,4 +452,229 @@ void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const
     if (a_first) { (void)hipEventRecord(T.ev[5], tq); (void)hipStreamWaitEvent(st, T.ev[5], 0); }
     (void)hipStreamWaitEvent(st, T.ev[2], 0);
     k_g16_rlc_verdict<<<nb, 64, 0, st>>>(n, io, flags, iov, d_ok, counters);
+}
+
+// ================================================================================================ which envelopes are bad (g16_localise.h)
+// After a batch check that did not stand, its scratch still holds every envelope's chain-A value e(rho_j A_j, B_j) (the value slots of
+// `io`), the weighted rho_j C_j (cbuf), the weights, the flags and the subgroup verdicts (ok).  The kernels below make one virtual envelope
+// per segment from them -- segment-ranged forms of the batch's own kernels, no Miller loop and no weighted point computed again -- run
+// the machine's chains with lane = segment, and leave one suspect byte per segment.
+namespace {
+enum { SEG_SPECIAL = 1u, SEG_BAD_SUBGROUP = 2u, SEG_LIVE = 4u };          // status bits of a segment
+enum { VSEG_NONE = 0u, VSEG_CHECK = 1u, VSEG_INFINITE = 2u };             // its virtual envelope: nothing live to check / in the slots / a point not finite (suspect)
+}  // namespace
+
+// block = segment: does it hold an envelope with a point at infinity, a live one whose B failed the subgroup check, a live one at all
+__global__ void __launch_bounds__(64) k_g16_seg_status(uint32_t n, G16Segments g, const uint8_t* flags, const uint8_t* ok, uint32_t* status) {
+    __shared__ uint32_t m;
+    if (threadIdx.x == 0) m = 0;
+    __syncthreads();
+    uint32_t bits = 0;
+    const uint32_t hi = g16_loc_hi(g, n, blockIdx.x);
+    for (uint32_t j = g16_loc_lo(g, blockIdx.x) + threadIdx.x; j < hi; j += 64) {
+        if (flags[j] == 2) bits |= SEG_SPECIAL;
+        if (flags[j] == 1) bits |= ok[j] ? SEG_LIVE : SEG_LIVE | SEG_BAD_SUBGROUP;
+    }
+    if (bits) atomicOr(&m, bits);
+    __syncthreads();
+    if (threadIdx.x == 0) status[blockIdx.x] = m;
+}
+// k_g16_rlc_terms + k_g16_rlc_scalars per segment: blockIdx.x = segment, blockIdx.y = t; scal[segment][t] = canonical words of S_{s,t}
+// (t < n_ic) and, from the block of t = 0, of 1 - S_{s,0} at t = n_ic
+__global__ void __launch_bounds__(64) k_g16_seg_terms(int kind, const uint8_t* in, uint64_t stride, const uint32_t* len, uint32_t n, G16Segments g, G16Vk vk, const uint32_t* rho, const uint8_t* flags, uint32_t* scal) {
+    __shared__ uint32_t sh[8 * 64];
+    const uint32_t t = threadIdx.x, seg = blockIdx.x, term = blockIdx.y, hi = g16_loc_hi(g, n, seg);
+    fr acc = fp_zero<FrParams>();
+    for (uint32_t j = g16_loc_lo(g, seg) + t; j < hi; j += 64) {
+        if (flags[j] != 1) continue;
+        G16Inputs h;
+        if (!g16_header(kind, vk, in + (uint64_t)j * stride, len[j], h)) continue;          // (live envelopes passed it already)
+        fr x;
+        if (g16_rlc_term(h, term, g16_rlc_weight(rho + 4 * j), x)) acc = fp_add(acc, x);
+    }
+    for (uint32_t s = 1; s < 64; s <<= 1) {
+        for (uint32_t k = 0; k < 8; k++) sh[k * 64 + t] = acc.v[k];
+        __syncthreads();
+        if ((t & (2 * s - 1)) == 0) { fr o; for (uint32_t k = 0; k < 8; k++) o.v[k] = sh[k * 64 + t + s]; acc = fp_add(acc, o); }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    uint32_t* out = scal + (size_t)seg * (vk.n_ic + 1) * 8;
+    uint32_t w[8]; fp_to_raw(w, acc);
+    for (uint32_t k = 0; k < 8; k++) out[(size_t)term * 8 + k] = w[k];
+    if (term == 0) { fp_to_raw(w, g16_rlc_one_minus(acc)); for (uint32_t k = 0; k < 8; k++) out[(size_t)vk.n_ic * 8 + k] = w[k]; }
+}
+// k_g16_rlc_fixed per segment: blockIdx.y = segment; blockIdx.x 0: L_{V,s} = sum_t S_{s,t} IC_t, 1: A_{V,s} = (1 - S_{s,0}) alpha.  pts: [L, A, C][30 words][nseg]
+__global__ void __launch_bounds__(256) k_g16_seg_fixed(G16Vk vk, const uint32_t* scal, uint32_t* pts) {
+    __shared__ uint32_t sh[30 * 256];
+    const uint32_t first = blockIdx.x == 0 ? 0u : vk.n_ic, count = blockIdx.x == 0 ? vk.n_ic : 1u, seg = blockIdx.y, nseg = gridDim.y;
+    const uint32_t* sc = scal + (size_t)seg * (vk.n_ic + 1) * 8;
+    g1_jac acc = jac_infinity<fq>();
+    for (uint32_t s = threadIdx.x; s < count * G16V_NWIN; s += 256) {
+        const uint32_t ic = first + s / G16V_NWIN, w = s % G16V_NWIN;
+        uint32_t k[8]; for (uint32_t j = 0; j < 8; j++) k[j] = sc[(size_t)ic * 8 + j];
+        const int32_t d = g16_ic_digit(k, w);
+        if (d == 0) continue;
+        const uint32_t* e = vk.ic_table + (((size_t)ic * G16V_NWIN + w) * G16V_NENT + (uint32_t)((d < 0 ? -d : d) - 1)) * 20;
+        g1_aff q; for (int j = 0; j < 10; j++) { q.x.v[j] = e[j]; q.y.v[j] = e[10 + j]; }
+        if (d < 0) q.y = fq_neg(q.y);
+        acc = jac_madd(acc, q);
+    }
+    acc = block_sum_jac(acc, sh);
+    if (threadIdx.x == 0) st_jac(pts + (size_t)30 * nseg * blockIdx.x, nseg, seg, acc);
+}
+// k_g1_sum over a segment's range: block = segment, out[segment] = sum of in[lo .. hi) (row length of `out`: the number of segments)
+__global__ void __launch_bounds__(256) k_g1_seg_sum(const uint32_t* in, uint32_t n_in, G16Segments g, uint32_t* out) {
+    __shared__ uint32_t sh[30 * 256];
+    g1_jac acc = jac_infinity<fq>();
+    const uint32_t hi = g16_loc_hi(g, n_in, blockIdx.x);
+    for (uint32_t j = g16_loc_lo(g, blockIdx.x) + threadIdx.x; j < hi; j += 256) acc = jac_add(acc, ld_jac(in, n_in, j));
+    acc = block_sum_jac(acc, sh);
+    if (threadIdx.x == 0) st_jac(out, g.count, blockIdx.x, acc);
+}
+// k_g16_rlc_virtual with lane = segment: the three pairs of every segment's virtual envelope in a slot buffer of nseg lanes (zeros where there
+// is nothing to check, as k_g16_pairs_vm leaves them for an envelope the machine does not take)
+__global__ void __launch_bounds__(64) k_g16_seg_virtual(G16Vk vk, uint32_t nseg, const uint32_t* pts, const uint32_t* status, uint32_t* iov, uint32_t* vstate) {
+    const uint32_t s = blockIdx.x * 64 + threadIdx.x, P = fq2vm::PAIR_SLOTS;
+    if (s >= nseg) return;
+    fq2 zero; f_set_zero(zero);
+    auto put = [&](uint32_t pair, const fq2& qx, const fq2& qy, const fq2& p) { vm_put(iov, nseg, s, P * pair + fq2vm::SLOT_QX, qx); vm_put(iov, nseg, s, P * pair + fq2vm::SLOT_QY, qy); vm_put(iov, nseg, s, P * pair + fq2vm::SLOT_P, p); };
+    if (status[s] & SEG_LIVE) {
+        const g1_jac Lv = ld_jac(pts, nseg, s);
+        g1_aff A, C;
+        if (jac_to_aff(A, ld_jac(pts + (size_t)30 * nseg, nseg, s)) && jac_to_aff(C, ld_jac(pts + (size_t)60 * nseg, nseg, s)) && !jac_is_inf(Lv)) {
+            vstate[s] = VSEG_CHECK;
+            put(0, vk.beta.x, vk.beta.y, fq2{A.x, A.y});
+            fq2 p1, p1z;
+            g16_vm_pair1(Lv, p1, p1z);
+            put(1, p1z, zero, p1);
+            const g1_aff nC = aff_neg(C);
+            put(2, vk.delta.x, vk.delta.y, fq2{nC.x, nC.y});
+            return;
+        }
+        vstate[s] = VSEG_INFINITE;
+    } else vstate[s] = VSEG_NONE;
+    for (uint32_t j = 0; j < 3; j++) put(j, zero, zero, zero);
+}
+// k_fq12_prod over a segment's range: block = segment multiplies the chain-A values of its live envelopes into the chain-A value of its
+// virtual envelope (fv: the six value slots of the virtual envelopes' buffer, row length nseg)
+__global__ void __launch_bounds__(64) k_fq12_seg_prod(const uint32_t* f, uint32_t n_in, const uint8_t* flags, G16Segments g, uint32_t* fv) {
+    __shared__ uint32_t sh[120 * 64];
+    const uint32_t t = threadIdx.x, seg = blockIdx.x, hi = g16_loc_hi(g, n_in, seg);
+    auto ld = [](const uint32_t* p, size_t n, size_t i) { fq2 c[6]; for (uint32_t s = 0; s < 6; s++) for (uint32_t k = 0; k < 10; k++) { c[s].c0.v[k] = p[(s * 20 + k) * n + i]; c[s].c1.v[k] = p[(s * 20 + 10 + k) * n + i]; } return fq12_from_coeffs(c); };
+    auto st = [](uint32_t* p, size_t n, size_t i, const fq12& x) { fq2 c[6]; fq12_to_coeffs(c, x); for (uint32_t s = 0; s < 6; s++) for (uint32_t k = 0; k < 10; k++) { p[(s * 20 + k) * n + i] = c[s].c0.v[k]; p[(s * 20 + 10 + k) * n + i] = c[s].c1.v[k]; } };
+    fq12 acc = fq12_one();
+    bool any = false;
+    for (uint32_t j = g16_loc_lo(g, seg) + t; j < hi; j += 64) {
+        if (flags[j] != 1) continue;
+        const fq12 x = ld(f, n_in, j);
+        acc = any ? fq12_mul(acc, x) : x; any = true;
+    }
+    if (t == 0) { const fq12 x = ld(fv, g.count, seg); acc = any ? fq12_mul(acc, x) : x; }
+    for (uint32_t s = 1; s < 64; s <<= 1) {
+        st(sh, 64, t, acc);
+        __syncthreads();
+        if ((t & (2 * s - 1)) == 0) acc = fq12_mul(acc, ld(sh, 64, t + s));
+        __syncthreads();
+    }
+    if (t == 0) st(fv, g.count, seg, acc);
+}
+// lane = segment.  Suspect: an envelope with a point at infinity, a live B outside the subgroup (the product argument needs every value in
+// the order-r group: such a segment is never cleared by its product), a virtual point that is not finite, or a product that is not one.
+__global__ void __launch_bounds__(64) k_g16_seg_suspects(uint32_t nseg, const uint32_t* iov, const uint32_t* status, const uint32_t* vstate, uint8_t* suspect) {
+    const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= nseg) return;
+    bool sus = (status[s] & (SEG_SPECIAL | SEG_BAD_SUBGROUP)) != 0 || vstate[s] == VSEG_INFINITE;
+    if (!sus && vstate[s] == VSEG_CHECK) {
+        bool good = fq2_eq(vm_get(iov, nseg, s, fq2vm::SLOT_RES), fq2_one());
+        for (uint32_t k = 1; k < 6; k++) good = good && f_is_zero(vm_get(iov, nseg, s, fq2vm::SLOT_RES + k));
+        sus = !good;
+    }
+    suspect[s] = sus ? 1 : 0;
+}
+// block = segment: the envelopes and lengths of a suspect segment to their place in the compacted buffer (off: g16_loc_offsets).  A segment's
+// bytes are one contiguous range on both sides: 16-byte or 4-byte vector copies where both ends are aligned, bytes for the rest.
+__global__ void __launch_bounds__(256) k_g16_seg_gather(const uint8_t* in, uint64_t stride, const uint32_t* len, uint32_t n, G16Segments g, const uint8_t* suspect, const uint32_t* off, uint8_t* out, uint32_t* out_len) {
+    const uint32_t seg = blockIdx.x, t = threadIdx.x;
+    if (!suspect[seg]) return;
+    const uint32_t lo = g16_loc_lo(g, seg), count = g16_loc_hi(g, n, seg) - lo;
+    for (uint32_t k = t; k < count; k += 256) out_len[off[seg] + k] = len[lo + k];
+    const uint8_t* src = in + (uint64_t)lo * stride;
+    uint8_t* dst = out + (uint64_t)off[seg] * stride;
+    const uint64_t bytes = (uint64_t)count * stride;
+    const uint64_t both = (uint64_t)(uintptr_t)src | (uint64_t)(uintptr_t)dst;
+    uint64_t done = 0;
+    if ((both & 15u) == 0) {
+        const uint64_t q = bytes / 16;
+        for (uint64_t i = t; i < q; i += 256) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+        done = q * 16;
+    } else if ((both & 3u) == 0) {
+        const uint64_t q = bytes / 4;
+        for (uint64_t i = t; i < q; i += 256) reinterpret_cast<uint32_t*>(dst)[i] = reinterpret_cast<const uint32_t*>(src)[i];
+        done = q * 4;
+    }
+    for (uint64_t i = done + t; i < bytes; i += 256) dst[i] = src[i];
+}
+// lane = envelope: the second pass's verdict of an envelope of a suspect segment back to its place
+__global__ void __launch_bounds__(64) k_g16_seg_scatter(uint32_t n, G16Segments g, const uint8_t* suspect, const uint32_t* off, const uint8_t* ok2, uint8_t* ok) {
+    const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n || !suspect[g16_loc_segment_of(g, j)]) return;
+    ok[j] = ok2[g16_loc_compact_index(g, off, j)];
+}
+
+namespace {
+struct LocLayout { size_t suspect, off, status, vstate, scal, pts, iov, total; };
+LocLayout loc_layout(uint32_t nseg, uint32_t n_ic) {
+    LocLayout L; size_t o = 0;
+    auto words = [&](size_t w) { const size_t at = o; o += (w * 4 + 255) & ~(size_t)255; return at; };
+    L.suspect = words((nseg + 3) / 4); L.off = words((size_t)nseg + 1); L.status = words(nseg); L.vstate = words(nseg);
+    L.scal = words((size_t)nseg * (n_ic + 1) * 8); L.pts = words((size_t)90 * nseg); L.iov = words((size_t)fq2vm::N_SLOTS * fq2vm::FQ2_W * nseg);
+    L.total = o;
+    return L;
+}
+}  // namespace
+size_t g16_loc_scratch_bytes(uint32_t nseg, uint32_t n_ic) { return loc_layout(nseg, n_ic).total; }
+size_t g16_loc_offsets_offset(uint32_t nseg, uint32_t n_ic) { return loc_layout(nseg, n_ic).off; }
+
+// d_rlc: the scratch of the g16_launch_verify_rlc call on these n envelopes that did not stand (complete: the caller has waited for it), d_ok
+// its verdicts.  Leaves one suspect byte per segment at the start of d_loc (g16_loc_scratch_bytes(g.count, vk.n_ic) bytes).
+void g16_launch_localise(int kind, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const G16Segments& g, const G16Vk& vk, const G16VmTables& T,
+                         const uint32_t* d_kconst, const uint32_t* d_lines, void* d_rlc, const uint8_t* d_ok, void* d_loc, hipStream_t st) {
+    if (!n || !g.count) return;
+    const RlcLayout Y = rlc_layout(n, vk.n_ic);
+    const LocLayout Z = loc_layout(g.count, vk.n_ic);
+    uint8_t *rb = reinterpret_cast<uint8_t*>(d_rlc), *lb = reinterpret_cast<uint8_t*>(d_loc);
+    auto W = [](uint8_t* base, size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
+    const uint32_t *io = W(rb, Y.io), *cbuf = W(rb, Y.cbuf), *rho = W(rb, Y.rho);
+    const uint8_t* flags = rb + Y.flags;
+    uint32_t *status = W(lb, Z.status), *vstate = W(lb, Z.vstate), *scal = W(lb, Z.scal), *pts = W(lb, Z.pts), *iov = W(lb, Z.iov);
+    const uint32_t nseg = g.count, nb = (nseg + 63) / 64, K = 4;
+    auto launch = [&](int chain, uint32_t* buf, const uint32_t* kconst, uint32_t script_len, hipStream_t s) {
+        fq2vm::Launch L{{T.code, T.off, K, T.consts}, T.script[chain], script_len, nseg, buf, 0, kconst};
+        k_fq2vm<<<(nseg + fq2vm::G - 1) / fq2vm::G, K * 64, (size_t)fq2vm::REGS_K4[chain] * fq2vm::FQ2_W * fq2vm::G * 4, s>>>(L);
+    };
+    (void)hipMemsetAsync(iov, 0, (size_t)fq2vm::N_SLOTS * fq2vm::FQ2_W * 4 * nseg, st);
+    k_g16_seg_status<<<nseg, 64, 0, st>>>(n, g, flags, d_ok, status);
+    k_g16_seg_terms<<<dim3(nseg, vk.n_ic), 64, 0, st>>>(kind, d_in, stride, d_len, n, g, vk, rho, flags, scal);
+    k_g16_seg_fixed<<<dim3(2, nseg), 256, 0, st>>>(vk, scal, pts);
+    k_g1_seg_sum<<<nseg, 256, 0, st>>>(cbuf, n, g, pts + (size_t)60 * nseg);
+    k_g16_seg_virtual<<<nb, 64, 0, st>>>(vk, nseg, pts, status, iov, vstate);
+    // chain B of the virtual envelopes beside their chain A, as in g16_launch_verify_vm; no subgroup chain: beta is the key's
+    (void)hipEventRecord(T.ev[0], st);
+    (void)hipStreamWaitEvent(T.side[0], T.ev[0], 0);
+    launch(3, iov + (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W * nseg, d_lines, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER_B) / 2), T.side[0]);
+    (void)hipEventRecord(T.ev[1], T.side[0]);
+    launch(0, iov, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), st);
+    k_fq12_seg_prod<<<nseg, 64, 0, st>>>(io + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W * n, n, flags, g, iov + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W * nseg);
+    (void)hipStreamWaitEvent(st, T.ev[1], 0);
+    launch(2, iov, d_kconst, (uint32_t)(sizeof(fq2vm::SCRIPT_FINISH) / 2), st);
+    k_g16_seg_suspects<<<nb, 64, 0, st>>>(nseg, iov, status, vstate, lb + Z.suspect);
+}
+// the suspect segments' envelopes and lengths into (d_in2, d_len2); d_off: g16_loc_offsets of the suspect bytes, in device memory
+void g16_launch_compact(const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const G16Segments& g, const uint8_t* d_suspect, const uint32_t* d_off,
+                        uint8_t* d_in2, uint32_t* d_len2, hipStream_t st) {
+    if (g.count) k_g16_seg_gather<<<g.count, 256, 0, st>>>(d_in, stride, d_len, n, g, d_suspect, d_off, d_in2, d_len2);
+}
+void g16_launch_scatter(uint32_t n, const G16Segments& g, const uint8_t* d_suspect, const uint32_t* d_off, const uint8_t* d_ok2, uint8_t* d_ok, hipStream_t st) {
+    if (n) k_g16_seg_scatter<<<(n + 63) / 64, 64, 0, st>>>(n, g, d_suspect, d_off, d_ok2, d_ok);
 }

@@ -682,14 +682,94 @@ void g16_release_all() {
     delete S; dev().g16 = nullptr;
 }
 
-// Verdicts of n envelopes.  The Fq2 machine (fq2vm.h) checks every envelope whose proof points are all finite; a batch that holds any
-// other valid encoding (a point at infinity drops a pair from the product) goes through the lane-per-chain kernels as a whole, which
-// handle those cases.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test knob) takes the lane-per-chain kernels for everything.
+// The per-envelope check of n envelopes that lie in device memory, verdicts into d_ok (and into ok, host memory, when it is given); waits for
+// them.  The Fq2 machine (fq2vm.h) checks every envelope whose proof points are all finite; a batch that holds any other valid encoding (a
+// point at infinity drops a pair from the product) goes through the lane-per-chain kernels as a whole, which handle those cases; use_vm = false
+// takes the lane-per-chain kernels for everything.  `e`: the state of the caller's earlier asynchronous calls on the stream.
+int verify_g16_device(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, uint8_t* d_ok, uint8_t* ok, bool use_vm, DevScope& mem, hipError_t e) {
+    hipStream_t st = dev().stream;
+    if (use_vm) {
+        uint8_t* d_scratch = nullptr; uint32_t* d_special = nullptr; uint32_t special = 0;
+        HIP_TRY(mem.alloc(&d_scratch, g16_vm_scratch_bytes(n))); HIP_TRY(mem.alloc(&d_special, 4));
+        if (e == hipSuccess) e = hipMemsetAsync(d_special, 0, 4, st);
+        if (e == hipSuccess) { g16_launch_verify_vm(kind, d_in, stride, d_len, n, K.vk, g16s().vm, K.vm_kconst, K.vm_lines, d_scratch, d_ok, d_special, st); e = hipGetLastError(); }
+        if (e == hipSuccess && ok) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&special, d_special, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+        if (!special) return 0;          // (the stream synchronisation above came after the chains' join)
+    }
+    uint8_t* d_scratch2 = nullptr;
+    HIP_TRY(mem.alloc(&d_scratch2, g16_verify_scratch_bytes(n)));
+    if (e == hipSuccess) { g16_launch_verify(kind, d_in, stride, d_len, n, K.vk, d_scratch2, d_ok, st); e = hipGetLastError(); }
+    if (e == hipSuccess && ok) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+    return 0;
+}
+
+// What a call did after a batch check that did not stand (ZKP_HIP_COUNTER_G16_VERIFY of zkp_hip_profile_read_kernel): added to the shard's
+// counters when the call returns, whichever way
+struct G16VerifyTally {
+    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    uint64_t segment_checks = 0, envelopes = 0;
+    explicit G16VerifyTally(Device& dv) : d(dv) {}
+    ~G16VerifyTally() {
+        d.g16_verify.launches += segment_checks; d.g16_verify.adds += envelopes;
+        d.g16_verify.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+// After a batch check of these n envelopes that did not stand (d_rlc: its scratch, d_ok / ok: its verdicts, on the device and on the host):
+// one check per segment says where the bad envelopes can be (g16_localise.h), and only the suspect segments' envelopes get the per-envelope
+// check.  *done = false: nothing was decided here and the caller verifies the whole batch (localisation switched off, or suspects in half of it).
+int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, uint8_t* d_rlc, uint8_t* d_ok, uint8_t* ok,
+                 const uint32_t counters[4], DevScope& mem, G16VerifyTally& tally, bool* done) {
+    *done = false;
+    if (env_int("ZKP_HIP_G16_LOCALISE", 1) == 0) return 0;
+    hipStream_t st = dev().stream;
+    // no envelope with a point at infinity, none live outside the subgroup and none live inside it: every envelope was refused at the parse, and those verdicts stand
+    if (counters[0] == 0 && counters[1] == 0 && std::all_of(ok, ok + n, [](uint8_t v) { return v == 0; })) { *done = true; return 0; }
+    const int forced = env_int("ZKP_HIP_G16_LOCALISE_SEGMENT", 0);
+    const G16Segments g = g16_loc_segments(n, forced > 0 ? (uint32_t)forced : 0u);
+    const uint32_t n_ic = K.vk.n_ic;
+    uint8_t* d_loc = nullptr;
+    HIP_TRY(mem.alloc(&d_loc, g16_loc_scratch_bytes(g.count, n_ic)));
+    std::vector<uint8_t> suspect(g.count);
+    g16_launch_localise(kind, d_in, stride, d_len, n, g, K.vk, g16s().vm, K.vm_kconst, K.vm_lines, d_rlc, d_ok, d_loc, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(suspect.data(), d_loc, g.count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    tally.segment_checks += g.count;
+    std::vector<uint32_t> off((size_t)g.count + 1);
+    const uint32_t m = g16_loc_offsets(g, n, suspect.data(), off.data());
+    if (g16_loc_whole_batch(m, n)) return 0;
+    *done = true;
+    if (m == 0) return 0;          // (every segment's check stands: the batch check failed on an anomaly of its own virtual envelope)
+    uint8_t *d_in2 = nullptr, *d_ok2 = nullptr; uint32_t* d_len2 = nullptr;
+    uint32_t* d_off = reinterpret_cast<uint32_t*>(d_loc + g16_loc_offsets_offset(g.count, n_ic));
+    HIP_TRY(mem.alloc(&d_in2, stride * m)); HIP_TRY(mem.alloc(&d_len2, 4ull * m)); HIP_TRY(mem.alloc(&d_ok2, m));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, st));
+    g16_launch_compact(d_in, stride, d_len, n, g, d_loc, d_off, d_in2, d_len2, st);
+    HIP_TRY(hipGetLastError());
+    tally.envelopes += m;
+    int rc = verify_g16_device(kind, K, d_in2, stride, d_len2, m, d_ok2, nullptr, true, mem, hipSuccess);
+    if (rc) return rc;
+    g16_launch_scatter(n, g, d_loc, d_off, d_ok2, d_ok, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Verdicts of n envelopes: one weighted pairing check for a large batch (g16_rlc.h); when it does not stand, the localisation pass and the
+// per-envelope check of the suspect envelopes, or of all of them.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test knob) takes the lane-per-chain
+// kernels for everything.
 int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
     G16Key& K = g16s().key[kind];
     if (!K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
     hipStream_t st = dev().stream;
-    uint8_t *d_in = nullptr, *d_ok = nullptr, *d_scratch = nullptr; uint32_t *d_len = nullptr, *d_special = nullptr;
+    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr;
     DevScope mem;
     // Chain B and the subgroup chain of the Fq2 machine run on the tables' side streams against d_scratch; DevScope only quiesces the
     // shard's main stream, so every early return below first waits for the whole device before the blocks go back to the pool.
@@ -698,7 +778,7 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
     hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
     static const int use_vm = env_int("ZKP_HIP_G16_VERIFY_VM", 1);
-    uint32_t special = 0;
+    std::unique_ptr<G16VerifyTally> tally;          // set once a batch check has not stood
     if (use_vm) {
         G16VmTables& T = g16s().vm;
         if (!T.ready) {
@@ -708,8 +788,8 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
         }
         // Large batches: one pairing check for all of them (g16_rlc.h) -- one Miller loop, one subgroup check and two 128-bit scalar
         // multiplications per envelope, the loops on gamma / delta and the final exponentiation once.  Its verdicts stand when the batch's
-        // product is one and no envelope needs the per-envelope treatment; otherwise (a tampered envelope, a point at infinity) the batch is
-        // verified again envelope by envelope below, so the answer is always the per-envelope one.
+        // product is one and no envelope needs the per-envelope treatment; otherwise (a tampered envelope, a point at infinity) the suspect
+        // envelopes, or all of them, are verified again envelope by envelope below, so the answer is always the per-envelope one.
         static const int rlc_min = env_int("ZKP_HIP_G16_BATCH_VERIFY_MIN", 8193);          // measured crossover: a single round of the per-envelope chains (<= 8192 envelopes) is faster than the batch check (profiles/r04_verify_g16_batch.json)
         if (rlc_min > 0 && n >= (uint64_t)rlc_min && !getenv("ZKP_HIP_NO_BATCH_VERIFY")) {
             const uint32_t n_ic = K.vk.n_ic;
@@ -730,22 +810,16 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
                 char msg[160]; snprintf(msg, sizeof msg, "the batch check did not stand (special %u, outside the subgroup %u, anomalies %u, product is one: %u)", counters[0], counters[1], counters[2], counters[3]);
                 return fail(ZKP_HIP_E_RUNTIME, msg);
             }
+            tally.reset(new G16VerifyTally(dev()));
+            bool done = false;
+            const int rc = localise_g16(kind, K, d_in, stride, d_len, (uint32_t)n, d_rlc, d_ok, ok, counters, mem, *tally, &done);
+            if (rc) return rc;
+            if (done) { quiesce.armed = false; return 0; }
+            tally->envelopes += n;
         }
-        HIP_TRY(mem.alloc(&d_scratch, g16_vm_scratch_bytes((uint32_t)n))); HIP_TRY(mem.alloc(&d_special, 4));
-        if (e == hipSuccess) e = hipMemsetAsync(d_special, 0, 4, st);
-        if (e == hipSuccess) { g16_launch_verify_vm(kind, d_in, stride, d_len, (uint32_t)n, K.vk, T, K.vm_kconst, K.vm_lines, d_scratch, d_ok, d_special, st); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&special, d_special, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
-        if (!special) { quiesce.armed = false; return 0; }          // (the stream synchronisation above came after the chains' join)
     }
-    uint8_t* d_scratch2 = nullptr;
-    HIP_TRY(mem.alloc(&d_scratch2, g16_verify_scratch_bytes((uint32_t)n)));
-    if (e == hipSuccess) { g16_launch_verify(kind, d_in, stride, d_len, (uint32_t)n, K.vk, d_scratch2, d_ok, st); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+    const int rc = verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem, e);
+    if (rc) return rc;
     quiesce.armed = false;
     return 0;
 }

@@ -12,9 +12,19 @@
 // (the finishing chain multiplies the key's constant e(-alpha, beta) in, hence 1 - s), and whose chain-A value is multiplied by the
 // product of the batch's chain-A values before the finishing chain runs.  sum_j rho_j L_j needs no curve arithmetic per envelope: L_j is
 // linear in the key's fixed points, so the S_t are sums in the scalar field and L_V is one walk of the key's window tables.
-// A batch that fails (or holds an envelope the machine leaves to the lane-per-chain path) is verified again envelope by envelope: the
-// verdicts are always those of the per-envelope check.  upstream has no batch verification; this is an internal fast path like the range
-// verifier's (bp_verify.h RlcView).
+// A batch that fails (or holds an envelope the machine leaves to the lane-per-chain path) is not thrown away: the same identity holds for any
+// subset of the envelopes, so the batch is cut into contiguous segments (g16_localise.h) and every segment s gets the check
+//     prod_{j in s} e(rho_j A_j, B_j) * e(-L_{V,s}, gamma) * e(-C_{V,s}, delta) * e(-(sum_{j in s} rho_j) alpha, beta) == 1
+// with its own virtual envelope -- S_{s,t}, L_{V,s}, A_{V,s}, C_{V,s} summed over the segment from the values the failed check left in device
+// memory, no Miller loop and no weighted point computed again (fq2vm_kernels.hip: k_g16_seg_*, lane = segment).  Only the envelopes of suspect
+// segments (product not one, a point at infinity, a live B outside the subgroup, a virtual point not finite) are verified again envelope by
+// envelope, or the whole batch when they are half of it: the verdicts are always those of the per-envelope check.
+// Soundness.  Segment s's check involves only the weights of its own envelopes, which are independent of everything else in the call, so it
+// accepts a segment that holds an invalid envelope with probability at most 2^-128, as the batch check does for the batch; a call makes the batch
+// check and at most one check per segment, and the union bound gives an error of at most (1 + nseg) 2^-128 per call (nseg <= 8192: below 2^-114).
+// Using the weights of the failed check again costs nothing: they never leave the device and the caller sees one bit per envelope, the
+// per-envelope verdict, which does not depend on them -- whoever made the envelopes had to fix them before the weights were drawn.
+// upstream has no batch verification; this is an internal fast path like the range verifier's (bp_verify.h RlcView).
 #pragma once
 #include "g16_verify.h"
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "g16_verify.h"
+#include "g16_localise.h"
 
 size_t g16_verify_scratch_bytes(uint32_t n);     // device scratch for n envelopes (Miller-loop values, parsed points)
 void g16_launch_verify(int kind, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const zkp::G16Vk& vk, void* d_scratch, uint8_t* d_ok, hipStream_t st);
@@ -36,3 +37,14 @@ size_t g16_rlc_rho_offset(uint32_t n, uint32_t n_ic);
 size_t g16_rlc_counters_offset(uint32_t n, uint32_t n_ic);
 void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const zkp::G16Vk& vk, const G16VmTables& T, const uint32_t* d_kconst,
                            const uint32_t* d_lines, void* d_scratch, uint8_t* d_ok, hipStream_t st);
+// Which envelopes are bad, after a batch check that did not stand (g16_localise.h): one virtual envelope per segment from what the check left in
+// d_rlc (its scratch, complete) and d_ok (its verdicts); leaves one suspect byte per segment at the start of d_loc (g16_loc_scratch_bytes(g.count,
+// vk.n_ic) bytes).  The caller turns those into offsets (g16_loc_offsets, to g16_loc_offsets_offset of d_loc), compacts the suspect segments'
+// envelopes, verifies them and scatters their verdicts back over d_ok.
+size_t g16_loc_scratch_bytes(uint32_t nseg, uint32_t n_ic);
+size_t g16_loc_offsets_offset(uint32_t nseg, uint32_t n_ic);
+void g16_launch_localise(int kind, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const zkp::G16Segments& g, const zkp::G16Vk& vk, const G16VmTables& T,
+                         const uint32_t* d_kconst, const uint32_t* d_lines, void* d_rlc, const uint8_t* d_ok, void* d_loc, hipStream_t st);
+void g16_launch_compact(const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const zkp::G16Segments& g, const uint8_t* d_suspect, const uint32_t* d_off,
+                        uint8_t* d_in2, uint32_t* d_len2, hipStream_t st);
+void g16_launch_scatter(uint32_t n, const zkp::G16Segments& g, const uint8_t* d_suspect, const uint32_t* d_off, const uint8_t* d_ok2, uint8_t* d_ok, hipStream_t st);

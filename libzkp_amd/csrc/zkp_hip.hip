@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <chrono>
 #include <sys/random.h>
 #include "bp_layout.h"
 #include "g16_steps.h"
@@ -331,6 +332,8 @@ struct Device {
         double ms = 0; uint64_t launches = 0, adds = 0;
     };
     KProf prof[3];                      // ZKP_HIP_KERNEL_MSM_ED25519 / _BN254_G1 / _BN254_G2
+    // ZKP_HIP_COUNTER_G16_VERIFY, always counted: what the Groth16 verifier did after batch checks that did not stand (g16_impl.inc: G16VerifyTally)
+    struct G16VerifyStats { double ms = 0; uint64_t launches = 0, adds = 0; } g16_verify;
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
 };
@@ -1224,6 +1227,7 @@ void zkp_hip_shutdown(void) try {
         for (auto& F : d->fam) { free_set(F.p1); for (auto& s : F.rd) free_set(s); F.ready = false; }
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
+        d->g16_verify = Device::G16VerifyStats();
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
@@ -1238,11 +1242,18 @@ void zkp_hip_profile_enable(int on) try {
 
 // accumulated over all shards
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset) try {
-    if (which < 0 || which > 2) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
+    if (which < 0 || which > ZKP_HIP_COUNTER_G16_VERIFY) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
     for (Device* d : shards) {
+        if (which == ZKP_HIP_COUNTER_G16_VERIFY) {          // host-side counters: no events to collect, and a shard that has not run yet is not initialised for them
+            std::lock_guard<std::mutex> dl(d->mu);
+            Device::G16VerifyStats& V = d->g16_verify;
+            tms += V.ms; tl += V.launches; ta += V.adds;
+            if (reset) V = Device::G16VerifyStats();
+            continue;
+        }
         Bind bind; int rc = bind.open(d);
         if (rc) return rc;
         HIP_TRY(hipDeviceSynchronize());

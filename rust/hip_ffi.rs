@@ -23,6 +23,9 @@ pub const OP_MEMBERSHIP: u32 = 4;
 pub const OP_IMPROVEMENT: u32 = 5;
 pub const OP_CONSISTENCY: u32 = 6;
 
+/// `zkp_hip_profile_read_kernel` id (not a kernel): segment checks run / envelopes verified again / host ms after Groth16 batch checks that did not stand.
+pub const ZKP_HIP_COUNTER_G16_VERIFY: c_int = 3;
+
 /// `zkp_hip_op`: one BatchOperation (utils/composition.rs:343-350) flattened; `kind` = the envelope scheme id.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
