@@ -242,6 +242,28 @@ typedef struct zkp_hip_op {
 } zkp_hip_op;
 int zkp_hip_process_batch(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, const uint8_t* seeds,
                           uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status);
+/* SELF-CHECK: a proof that does not verify against its own op never leaves the GPU.  OR this flag into `kind` of EVERY op of a call (a call with
+ * the flag on some ops only: ZKP_HIP_E_ARGUMENT, "self-check is a property of the whole batch", before any device work).  zkp_hip_process_batch,
+ * zkp_hip_batch_prove and zkp_hip_batch_prove_async + zkp_hip_batch_wait then prove as always, and the waiting half runs each scheme's verifier --
+ * the kernels behind zkp_hip_verify_*_batch, batch checks, fallbacks and switches included -- over that variant's envelopes where they lie in
+ * HBM, against the op's own staged parameters, before lengths, statuses, offsets and the packed output are produced:
+ *   RANGE verify_range(proof, min, max) | THRESHOLD verify_threshold(proof, threshold) | CONSISTENCY verify_consistency(proof)
+ *   IMPROVEMENT verify_improvement(proof, old)
+ *   EQUALITY verify_equality(proof, a, b): the pairing check AND the envelope's 32-byte commitment equals the MiMC commitment of a
+ *   MEMBERSHIP verify_membership(proof, set): the pairing check AND the embedded count and elements equal the staged set IN THE STAGED ORDER
+ *     (stricter than upstream's multiset comparison, set_membership.rs:40-70; the prover embeds the set as given, so an honest envelope passes).
+ * An op whose envelope is not accepted gets status ZKP_HIP_PROOF_GENERATION_FAILED, length 0 and no bytes in the output (out_off stays a compact
+ * prefix sum; the call returns 1); ops that failed validation keep their status; when every envelope is accepted the bytes, offsets and statuses
+ * are those of the unflagged batch under the same seeds.  No envelope crosses to the host for this: the host reads verdict-sized data only (the
+ * batch checks' result words and counters, suspect maps, one verdict byte per Groth16 envelope).  The schemes' verifiers run one after the other
+ * on the shard's stream, each shard checks its own slice, and a second batch may be proving on the shard's other lane meanwhile.
+ * zkp_hip_plan_shards and zkp_hip_process_batch_bytes return for flagged ops what they return for the same ops unflagged.
+ * Counted per shard, always: zkp_hip_profile_read_kernel(ZKP_HIP_COUNTER_BATCH_SELF_CHECK, ...).
+ * Diagnostic: ZKP_HIP_SELF_CHECK_FLIP=<global op index>:<byte offset>, read on every prove of a flagged batch: after proving and before
+ * verification one small kernel flips bit 0 of that byte of that op's arena record (tests see the check refuse something this way).  An index
+ * beyond the batch, an op without a record (refused by validation), an offset beyond the op's fixed-stride arena record or a malformed value:
+ * ZKP_HIP_E_ARGUMENT.  No effect on unflagged batches. */
+#define ZKP_HIP_OP_SELF_CHECK 0x100u
 /* Capacity that is enough for any outcome of zkp_hip_process_batch on these ops (improvement envelopes counted at
  * zkp_hip_improvement_max_bytes()): callers size `out` with it instead of proving twice.  No device work. */
 int zkp_hip_process_batch_bytes(uint64_t n, const zkp_hip_op* ops, uint64_t* max_total);
@@ -283,7 +305,11 @@ enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_
         * zkp_hip_profile_enable needed), summed over the shards, same `reset`.  *launches = segment checks run (virtual envelopes sent through the
         * pairing chains by localisation passes); *point_adds = envelopes given the per-envelope check after a failed batch check (the compacted
         * suspects, or n when the whole batch was verified again); *ms = host wall time from the failed check's verdict to the call's return. */
-       ZKP_HIP_COUNTER_G16_VERIFY = 3 };
+       ZKP_HIP_COUNTER_G16_VERIFY = 3,
+       /* Not a kernel: the self-check of flagged batches (ZKP_HIP_OP_SELF_CHECK).  Always counted, summed over the shards, same `reset`.
+        * *launches = ops whose envelope went through its verifier; *point_adds = ops refused by the self-check; *ms = host wall time from the end
+        * of proving to the end of verification (verdicts applied, proofs packed). */
+       ZKP_HIP_COUNTER_BATCH_SELF_CHECK = 4 };
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset);
 int zkp_hip_profile_read(double* msm_ms, uint64_t* msm_launches, uint64_t* msm_point_adds, int reset);
 /* Tunable (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned

@@ -541,6 +541,17 @@ def groth16_verify_counters(reset=True):
     return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
 
 
+def batch_self_check_counters(reset=True):
+    """What the self-check of flagged batches (process_ops / process_batch with self_check=True; ZKP_HIP_OP_SELF_CHECK) did, summed over the
+    shards since the last reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_BATCH_SELF_CHECK; always counted): {"launches": ops whose
+    envelope went through its verifier, "point_adds": ops the self-check refused, "ms": host wall time from the end of proving to the end of
+    verification}.  reset=True zeroes the counters."""
+    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_BATCH_SELF_CHECK, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
+                  "zkp_hip_profile_read_kernel")
+    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+
+
 def verify_equality_with_commitment_batch(proofs, commitments):
     """Batched verify_equality_with_commitment (equality_proof.rs:34-60): the envelope must carry exactly that commitment."""
     blobs = [bytes(p) for p in proofs]
@@ -747,8 +758,9 @@ def batch_add_consistency_proof(batch_id, data):
     _with_batch(batch_id, ("consistency", tuple(data)))
 
 
-def process_batch(batch_id, seeds=None):
-    """batch.rs:110-140: consumes the batch (even if proving fails), returns proofs in insertion order."""
+def process_batch(batch_id, seeds=None, self_check=False):
+    """batch.rs:110-140: consumes the batch (even if proving fails), returns proofs in insertion order.  self_check=True: every proof is
+    verified on the GPU against its own op before it is returned (process_ops); a refused op fails the batch like any failed op."""
     with _registry_lock:
         if batch_id not in _registry:
             raise ValueError("Invalid batch ID: %d" % batch_id)
@@ -757,12 +769,14 @@ def process_batch(batch_id, seeds=None):
     for op in ops:
         if op[0] == "membership" and len(op[2]) > MAX_SET_SIZE:      # set_membership.rs:14 (validate_set_size at prove time)
             raise ValueError("set size %d exceeds maximum allowed size %d" % (len(op[2]), MAX_SET_SIZE))
-    return process_ops(ops, seeds)
+    return process_ops(ops, seeds, self_check)
 
 
-def process_ops(ops, seeds=None):
+def process_ops(ops, seeds=None, self_check=False):
     """The whole mixed batch through ONE C-ABI call (zkp_hip_process_batch, the compiled replacement of
-    advanced::process_batch); same result as prove_ops, without the per-variant Python marshalling."""
+    advanced::process_batch); same result as prove_ops, without the per-variant Python marshalling.  self_check=True sets
+    ZKP_HIP_OP_SELF_CHECK on every op: each scheme's verifier runs over the proofs where they lie in HBM, against the op's own parameters,
+    before anything is returned; the proofs are the same bytes, and an op whose proof is refused fails the batch (status 2)."""
     n = len(ops)
     if n == 0:
         return []
@@ -777,7 +791,7 @@ def process_ops(ops, seeds=None):
     for i, o in enumerate(ops):
         k = o[0]
         e = arr[i]
-        e.kind = code[k]
+        e.kind = code[k] | (_native.OP_SELF_CHECK if self_check else 0)
         if k == "range":
             e.a, e.b, e.c = o[1], o[2], o[3]; cap += 1478
         elif k == "equality":

@@ -14,6 +14,10 @@
 //
 // zkp_hip_process_batch = stage + prove + fetch; the staged entry points exist so that a caller (bench.py) can keep a batch
 // resident and time the proving alone.
+//
+// A batch whose ops carry ZKP_HIP_OP_SELF_CHECK is proved the same way up to the join of the variants' streams; the three pack kernels then
+// wait for the waiting half (wait_shard -> self_check_shard), which first runs every scheme's verifier over that variant's arena rows
+// against the ops' staged parameters (batch_self_check.h) and turns a refused envelope into a failed op.
 namespace {
 
 constexpr uint32_t LEN_DYN = 0xffffffffu;
@@ -76,6 +80,31 @@ __global__ void __launch_bounds__(64) k_consistency_digest(uint8_t* img, uint64_
     if (i >= n || lens[i] == 0) return;
     uint8_t* o = img + (uint64_t)i * stride;
     sha256_bytes(o + lens[i] - 32, o + 14, 32ull * counts[i]);
+}
+
+// ---- the self-check of a flagged batch (batch_self_check.h): tiny kernels bound by launch latency, no scratch (profiles/self_check.json)
+static_assert(SC_LEN_DYN == LEN_DYN && SC_DYN_LEN_STATUS == DYN_LEN_STATUS && SC_STATUS_REFUSED == ZKP_HIP_PROOF_GENERATION_FAILED && SC_KINDS == ZKP_HIP_OP_CONSISTENCY + 1,
+              "batch_self_check.h mirrors the pack view and the op kinds");
+// lane = op: the lens rows the verifiers take, and the row <-> op map
+__global__ void __launch_bounds__(256) k_self_check_rows(SelfCheckView V) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < V.n) step_self_check_rows(V, i);
+}
+// lane = Groth16 row: the envelope's commitment / embedded set against the staged value / set, ANDed into the row's verdict
+__global__ void __launch_bounds__(64) k_self_check_bind_g16(SelfCheckView V) {
+    step_self_check_bind_g16(V, blockIdx.x * 64 + threadIdx.x);
+}
+// lane = op: verdict rows back to op order, after k_batch_lens and before k_batch_scan; counters[0] += ops verified, [1] += ops refused
+__global__ void __launch_bounds__(256) k_self_check_apply(SelfCheckView V, uint32_t* counters) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= V.n) return;
+    const uint32_t f = step_self_check_apply(V, i);
+    if (f & 1u) atomicAdd(counters, 1u);
+    if (f & 2u) atomicAdd(counters + 1, 1u);
+}
+// ZKP_HIP_SELF_CHECK_FLIP: one lane flips bit 0 of one byte of op j's arena record
+__global__ void __launch_bounds__(64) k_self_check_flip(uint8_t* arena, const uint64_t* src_off, uint32_t j, uint32_t byte) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) step_self_check_flip(arena, src_off, j, byte);
 }
 
 size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -175,6 +204,14 @@ struct ShardPlan {
     size_t a_range = 0, a_eq = 0, a_mem = 0, a_imp = 0, a_thr = 0, a_con = 0, a_dlen = 0, a_dst = 0;
     // offsets into d_meta (results): out_off[n + 1] | status[n] | len[n]
     size_t m_off = 0, m_status = 0, m_len = 0;
+    // self-check (ZKP_HIP_OP_SELF_CHECK): further offsets into d_in -- the thresholds, every op's variant, the verifiers' lens / verdict rows and
+    // the row <-> op map (written on the device), the two counters -- and the variants' geometry, indexed by op kind
+    bool self_check = false;
+    size_t i_thr = 0, i_var = 0, i_rlen = 0, i_rop = 0, i_rok = 0, i_oprow = 0, i_cnt = 0;
+    uint64_t v_base[SC_KINDS] = {0}, v_stride[SC_KINDS] = {0};
+    uint32_t v_row0[SC_KINDS] = {0}, v_rows[SC_KINDS] = {0};
+    std::vector<uint8_t> op_variant;       // [n] the op's kind when it has an arena row, else 0
+    int64_t flip_op = -1; uint32_t flip_byte = 0;      // ZKP_HIP_SELF_CHECK_FLIP as read by the last prove: local op index (-1: none), byte of its record
     bool proved = false;
     hipEvent_t finished = nullptr;         // recorded behind the last kernel of a prove; zkp_hip_batch_wait synchronises on it
     bool in_flight = false;
@@ -190,6 +227,7 @@ struct zkp_hip_batch {
     std::vector<ShardPlan> shards;
     uint64_t max_total = 0;
     bool proved = false;
+    bool self_check = false;               // every op carries ZKP_HIP_OP_SELF_CHECK
 };
 
 extern "C" int zkp_hip_batch_wait(zkp_hip_batch* batch);
@@ -203,8 +241,18 @@ template <class F> int for_each_shard(zkp_hip_batch& B, F f, bool init = true) {
     return for_each_device(devs, [&](size_t k) { return f(B.shards[k]); }, init);
 }
 
+// the op's kind without the batch-wide ZKP_HIP_OP_SELF_CHECK flag: every reader of `kind` goes through this
+uint32_t op_kind(const zkp_hip_op& o) { return o.kind & ~ZKP_HIP_OP_SELF_CHECK; }
+// a batch is self-checked as a whole: *flagged = every op carries the flag; some but not all: ZKP_HIP_E_ARGUMENT
+int self_check_flag(uint64_t n, const zkp_hip_op* ops, bool* flagged) {
+    uint64_t with = 0;
+    for (uint64_t i = 0; i < n; i++) with += (ops[i].kind & ZKP_HIP_OP_SELF_CHECK) ? 1 : 0;
+    if (with != 0 && with != n) return fail(ZKP_HIP_E_ARGUMENT, "self-check is a property of the whole batch: ZKP_HIP_OP_SELF_CHECK must be set on every op of a call or on none");
+    if (flagged) *flagged = n != 0 && with == n;
+    return 0;
+}
 uint64_t op_max_bytes(const zkp_hip_op& o) {
-    switch (o.kind) {
+    switch (op_kind(o)) {
         case ZKP_HIP_OP_RANGE: return RANGE_PROOF_BYTES;
         case ZKP_HIP_OP_EQUALITY: return 298;
         case ZKP_HIP_OP_THRESHOLD: return threshold_envelope_bytes(6);
@@ -214,10 +262,10 @@ uint64_t op_max_bytes(const zkp_hip_op& o) {
         default: return 0;
     }
 }
-int check_ops(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists) {
+int check_ops(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, bool* self_check = nullptr) {
     uint64_t list_total = 0;
     for (uint64_t i = 0; i < n; i++) {
-        const uint32_t k = ops[i].kind;
+        const uint32_t k = op_kind(ops[i]);
         if (k == ZKP_HIP_OP_THRESHOLD || k == ZKP_HIP_OP_CONSISTENCY) {      // (a membership set is read only when count <= 64)
             list_total += ops[i].count;
             if (list_total > ZKP_MAX_LIST_VALUES) return fail(ZKP_HIP_E_ARGUMENT, "value lists too long: at most 2^28 values per call (split the batch)");
@@ -226,16 +274,16 @@ int check_ops(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists) {
         if ((k == ZKP_HIP_OP_THRESHOLD || k == ZKP_HIP_OP_MEMBERSHIP || k == ZKP_HIP_OP_CONSISTENCY) && ops[i].count && !lists)
             return fail(ZKP_HIP_E_ARGUMENT, "operation refers to value lists but lists is null");
     }
-    return 0;
+    return self_check_flag(n, ops, self_check);
 }
 
 // Which shard proves which op: every variant's bucket (ops of one kind, in the caller's order) is cut into `shards` contiguous
 // slices whose sizes differ by at most one, so all GPUs run the same kernel mix (SURVEY 8e).  Pure host logic.
 void plan_shards(uint64_t n, const zkp_hip_op* ops, uint32_t shards, uint32_t* shard_of_op) {
     uint64_t count[7] = {0, 0, 0, 0, 0, 0, 0}, seen[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (uint64_t i = 0; i < n; i++) count[ops[i].kind]++;
+    for (uint64_t i = 0; i < n; i++) count[op_kind(ops[i])]++;
     for (uint64_t i = 0; i < n; i++) {
-        const uint32_t k = ops[i].kind;
+        const uint32_t k = op_kind(ops[i]);
         const uint64_t q = seen[k]++, m = count[k];
         // slice s holds bucket positions [m*s/S, m*(s+1)/S): the owner of position q is the largest s with m*s/S <= q
         uint32_t s = (uint32_t)(((q + 1) * shards - 1) / m);
@@ -246,8 +294,9 @@ void plan_shards(uint64_t n, const zkp_hip_op* ops, uint32_t shards, uint32_t* s
 }
 
 // builds one shard's staging image from its ops (host only), uploads it, and allocates the device blocks
-int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, const uint8_t* seeds) {
+int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, const uint8_t* seeds, bool self_check) {
     const uint32_t n = P.n;
+    P.self_check = self_check;
     BatchState* BS = nullptr; int rc;
     if ((rc = batch_state(&BS))) return rc;
     // ---- pass 1: count rows per variant, validate what the host validates
@@ -256,7 +305,7 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
     for (uint32_t j = 0; j < n; j++) {
         const zkp_hip_op& o = ops[P.gidx[j]];
         P.max_total += op_max_bytes(o);
-        switch (o.kind) {
+        switch (op_kind(o)) {
             case ZKP_HIP_OP_RANGE: P.n_range++; break;
             case ZKP_HIP_OP_EQUALITY: row_ok[j] = equality_ok(o.a, o.b); P.n_eq += row_ok[j]; break;
             case ZKP_HIP_OP_MEMBERSHIP:
@@ -282,13 +331,27 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
     P.i_io = take(8ull * P.n_imp); P.i_in = take(8ull * P.n_imp);
     P.i_tseed = take(32ull * P.n_thr); P.i_cseed = take(32ull * P.n_con); P.i_ccount = take(4ull * P.n_con); P.i_clen = take(4ull * P.n_con);
     P.i_src = take(8ull * n); P.i_lenf = take(4ull * n); P.i_dix = take(4ull * n); P.i_dkind = take(n); P.i_stf = take(4ull * n);
+    const uint64_t stride_thr = threshold_envelope_bytes(6);
+    if (self_check) {
+        // what the verifier cores need beside the prover's inputs: the thresholds (the prover takes them through the framing), and rows of
+        // lens / verdicts per variant, built on the device (k_self_check_rows); a variant's rows start at a multiple of SC_ROW_ALIGN
+        const uint32_t rows[SC_KINDS] = {0, P.n_range, P.n_eq, P.n_thr, P.n_mem, P.n_imp, P.n_con};
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < SC_KINDS; k++) { P.v_row0[k] = total; P.v_rows[k] = rows[k]; total += (rows[k] + SC_ROW_ALIGN - 1) / SC_ROW_ALIGN * SC_ROW_ALIGN; }
+        P.i_thr = take(8ull * P.n_thr); P.i_var = take(n); P.i_rlen = take(4ull * total); P.i_rop = take(4ull * total); P.i_rok = take(total);
+        P.i_oprow = take(4ull * n); P.i_cnt = take(8);
+    }
     P.in_bytes = off;
     off = 0;
-    const uint64_t stride_thr = threshold_envelope_bytes(6);
     P.a_range = take((size_t)RANGE_PROOF_BYTES * P.n_range); P.a_eq = take(298ull * P.n_eq); P.a_mem = take(P.stride_mem * P.n_mem);
     P.a_imp = take((size_t)STARK_MAX_ENVELOPE * P.n_imp); P.a_thr = take(stride_thr * P.n_thr); P.a_con = take(P.stride_con * P.n_con);
     P.a_dlen = take(4ull * (P.n_range + P.n_imp)); P.a_dst = take(4ull * P.n_range);
     P.arena_bytes = off;
+    {
+        const uint64_t base[SC_KINDS] = {0, P.a_range, P.a_eq, P.a_thr, P.a_mem, P.a_imp, P.a_con};
+        const uint64_t stride[SC_KINDS] = {0, RANGE_PROOF_BYTES, 298, stride_thr, P.stride_mem, STARK_MAX_ENVELOPE, P.stride_con};
+        for (uint32_t k = 0; k < SC_KINDS; k++) { P.v_base[k] = base[k]; P.v_stride[k] = stride[k]; }
+    }
     off = 0;
     P.m_off = take(8ull * (n + 1)); P.m_status = take(4ull * n); P.m_len = take(4ull * n);
     P.meta_bytes = off;
@@ -311,7 +374,7 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
         const zkp_hip_op& o = ops[gi];
         const uint8_t* sd = seeds + 32 * gi;
         src[j] = 0; lenf[j] = 0; dix[j] = 0; dkind[j] = DYN_NONE; stf[j] = row_ok[j] ? ZKP_HIP_OK : ZKP_HIP_INVALID_INPUT;
-        switch (o.kind) {
+        switch (op_kind(o)) {
             case ZKP_HIP_OP_RANGE:
                 u64p(P.i_rv)[r] = o.a; u64p(P.i_rmin)[r] = o.b; u64p(P.i_rmax)[r] = o.c; memcpy(h + P.i_rseed + 32ull * r, sd, 32);
                 src[j] = P.a_range + (uint64_t)RANGE_PROOF_BYTES * r; lenf[j] = LEN_DYN; dix[j] = r; dkind[j] = DYN_LEN_STATUS; r++;
@@ -360,6 +423,16 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
             u32p(P.i_ccount)[k] = c_counts[k]; u32p(P.i_clen)[k] = P.con_lens[k];
         }
     }
+    if (self_check) {
+        P.op_variant.assign(n, 0);
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t k = op_kind(ops[P.gidx[j]]);
+            const bool validated_on_host = k == ZKP_HIP_OP_EQUALITY || k == ZKP_HIP_OP_MEMBERSHIP || k == ZKP_HIP_OP_IMPROVEMENT;      // (their rows hold valid ops only)
+            P.op_variant[j] = validated_on_host && !row_ok[j] ? 0 : (uint8_t)k;
+        }
+        if (n) memcpy(h + P.i_var, P.op_variant.data(), n);
+        if (P.n_thr) memcpy(h + P.i_thr, t_thr.data(), 8ull * P.n_thr);
+    }
     // ---- device blocks + the one upload
     DevPool& pool = dev().pool;
     P.generation = dev().generation;
@@ -372,6 +445,16 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
     if (P.in_bytes) HIP_TRY(hipMemcpyAsync(P.d_in, h, P.in_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));                 // the pinned image is reused by the next staging on this shard
     return 0;
+}
+
+PackView pack_view(const ShardPlan& P) {
+    uint8_t *in = P.d_in, *ar = P.d_arena;
+    PackView V{};
+    V.n = P.n; V.src_off = (const uint64_t*)(in + P.i_src); V.len_fixed = (const uint32_t*)(in + P.i_lenf); V.dyn_ix = (const uint32_t*)(in + P.i_dix);
+    V.dyn_kind = in + P.i_dkind; V.status_fixed = (const int32_t*)(in + P.i_stf); V.dyn_len = (const uint32_t*)(ar + P.a_dlen); V.dyn_status = (const int32_t*)(ar + P.a_dst);
+    V.len = (uint32_t*)(P.d_meta + P.m_len); V.status = (int32_t*)(P.d_meta + P.m_status); V.out_off = (uint64_t*)(P.d_meta + P.m_off);
+    V.arena = ar; V.out = P.d_out;
+    return V;
 }
 
 // enqueues the whole proving of one shard's share on one lane of streams and returns; wait_shard blocks until it is done
@@ -443,12 +526,10 @@ int launch_shard_enqueue(ShardPlan& P) {
         HIP_TRY(hipEventRecord(LN.done[1], s));
     }
     for (int k = 0; k < 4; k++) if (used[k]) HIP_TRY(hipStreamWaitEvent(st, LN.done[k], 0));
-    PackView V{};
-    V.n = n; V.src_off = (const uint64_t*)(in + P.i_src); V.len_fixed = (const uint32_t*)(in + P.i_lenf); V.dyn_ix = (const uint32_t*)(in + P.i_dix);
-    V.dyn_kind = in + P.i_dkind; V.status_fixed = (const int32_t*)(in + P.i_stf); V.dyn_len = (const uint32_t*)(ar + P.a_dlen); V.dyn_status = (const int32_t*)(ar + P.a_dst);
-    V.len = (uint32_t*)(P.d_meta + P.m_len); V.status = (int32_t*)(P.d_meta + P.m_status); V.out_off = (uint64_t*)(P.d_meta + P.m_off);
-    V.arena = ar; V.out = P.d_out;
-    if (n) {
+    const PackView V = pack_view(P);
+    if (n && P.self_check) {
+        // the lengths, the prefix sum and the packing wait for the verdicts: self_check_shard runs them behind the verifiers
+    } else if (n) {
         ZKP_TRACED("k_batch_lens+scan+pack", st, k_batch_lens<<<(n + 255) / 256, 256, 0, st>>>(V); k_batch_scan<<<1, 1024, 0, st>>>(V); k_batch_pack<<<n, 256, 0, st>>>(V));
     } else {
         HIP_TRY(hipMemsetAsync(P.d_meta + P.m_off, 0, 8, st));        // a shard without ops (fewer ops than shards): out_off[0] = 0
@@ -472,11 +553,72 @@ int launch_shard(ShardPlan& P) {
     }
     return rc;
 }
+// The self-check of a proved shard (every envelope is in the arena, nothing of this batch is running): each scheme's verifier, one after the
+// other on the shard's stream, over that variant's arena rows against the staged parameters; the Groth16 binding; then the pack kernels with
+// the verdicts applied between the lengths and their prefix sum.  The host reads what the verifier cores read, and eight bytes of counters.
+int self_check_shard(ShardPlan& P) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = P.n;
+    hipStream_t st = dev().stream;
+    uint8_t *in = P.d_in, *ar = P.d_arena;
+    const PackView W = pack_view(P);
+    SelfCheckView V{};
+    V.n = n; V.src_off = W.src_off; V.len_fixed = W.len_fixed; V.dyn_ix = W.dyn_ix; V.dyn_kind = W.dyn_kind; V.status_fixed = W.status_fixed;
+    V.dyn_len = W.dyn_len; V.dyn_status = W.dyn_status; V.op_variant = in + P.i_var;
+    for (uint32_t k = 0; k < SC_KINDS; k++) { V.base[k] = P.v_base[k]; V.stride[k] = P.v_stride[k]; V.row0[k] = P.v_row0[k]; V.rows[k] = P.v_rows[k]; }
+    V.row_len = (uint32_t*)(in + P.i_rlen); V.row_op = (uint32_t*)(in + P.i_rop); V.row_ok = in + P.i_rok; V.op_row = (uint32_t*)(in + P.i_oprow);
+    V.len = W.len; V.status = W.status;
+    V.arena = ar; V.eq_value = (const uint64_t*)(in + P.i_ev); V.mem_sets = (const uint64_t*)(in + P.i_msets); V.mem_len = (const uint32_t*)(in + P.i_mlen);
+    uint32_t* d_cnt = (uint32_t*)(in + P.i_cnt);
+    int rc;
+    if (P.flip_op >= 0) k_self_check_flip<<<1, 64, 0, st>>>(ar, V.src_off, (uint32_t)P.flip_op, P.flip_byte);
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, st));
+    k_self_check_rows<<<(n + 255) / 256, 256, 0, st>>>(V);
+    HIP_TRY(hipGetLastError());
+    auto lens = [&](uint32_t k) { return (const uint32_t*)(V.row_len + P.v_row0[k]); };
+    auto oks = [&](uint32_t k) { return V.row_ok + P.v_row0[k]; };
+    if (P.n_range && (rc = verify_bp_device(1, P.n_range, ar + P.a_range, RANGE_PROOF_BYTES, lens(ZKP_HIP_OP_RANGE), (const uint64_t*)(in + P.i_rmin), (const uint64_t*)(in + P.i_rmax),
+                                            oks(ZKP_HIP_OP_RANGE), nullptr, nullptr))) return rc;
+    if (P.n_thr && (rc = verify_bp_device(3, P.n_thr, ar + P.a_thr, P.v_stride[ZKP_HIP_OP_THRESHOLD], lens(ZKP_HIP_OP_THRESHOLD), (const uint64_t*)(in + P.i_thr), nullptr,
+                                          oks(ZKP_HIP_OP_THRESHOLD), nullptr, nullptr))) return rc;
+    if (P.n_con) {
+        std::vector<uint32_t> jobs(P.n_con);          // k - 1 range proofs for a framed list of k values (none for a list the framing refused)
+        for (uint32_t k = 0; k < P.n_con; k++) jobs[k] = P.con_lens[k] && P.con_counts[k] ? P.con_counts[k] - 1 : 0;
+        if ((rc = verify_bp_device(6, P.n_con, ar + P.a_con, P.stride_con, lens(ZKP_HIP_OP_CONSISTENCY), nullptr, nullptr, oks(ZKP_HIP_OP_CONSISTENCY), jobs.data(), nullptr))) return rc;
+    }
+    if (P.n_eq || P.n_mem) {
+        DevScope mem;
+        struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;      // as verify_g16_host: the chains' side streams
+        std::vector<uint8_t> h_ok(P.n_eq > P.n_mem ? P.n_eq : P.n_mem);      // the batch check's verdicts, read by its localisation pass
+        if (P.n_eq && (rc = verify_g16_core(G16_EQUALITY, P.n_eq, ar + P.a_eq, 298, lens(ZKP_HIP_OP_EQUALITY), oks(ZKP_HIP_OP_EQUALITY), h_ok.data(), mem, hipSuccess))) return rc;
+        if (P.n_mem && (rc = verify_g16_core(G16_MEMBERSHIP, P.n_mem, ar + P.a_mem, P.stride_mem, lens(ZKP_HIP_OP_MEMBERSHIP), oks(ZKP_HIP_OP_MEMBERSHIP), h_ok.data(), mem, hipSuccess))) return rc;
+        quiesce.armed = false;
+        if ((rc = ensure_mimc_dev())) return rc;
+        V.mimc_c = g16s().mimc_dev;
+        k_self_check_bind_g16<<<(P.n_eq + P.n_mem + 63) / 64, 64, 0, st>>>(V);
+        HIP_TRY(hipGetLastError());
+    }
+    if (P.n_imp && (rc = verify_stark_device(P.n_imp, ar + P.a_imp, STARK_MAX_ENVELOPE, lens(ZKP_HIP_OP_IMPROVEMENT), (const uint64_t*)(in + P.i_io), oks(ZKP_HIP_OP_IMPROVEMENT)))) return rc;
+    k_batch_lens<<<(n + 255) / 256, 256, 0, st>>>(W);
+    k_self_check_apply<<<(n + 255) / 256, 256, 0, st>>>(V, d_cnt);
+    k_batch_scan<<<1, 1024, 0, st>>>(W);
+    k_batch_pack<<<n, 256, 0, st>>>(W);
+    HIP_TRY(hipGetLastError());
+    uint32_t cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    Device::SelfCheckStats& C = dev().self_check;
+    C.verified += cnt[0]; C.refused += cnt[1];
+    C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
 int wait_shard(ShardPlan& P) {
     if (P.generation != dev().generation) return fail(ZKP_HIP_E_ARGUMENT, "the batch was staged before zkp_hip_shutdown: stage it again");
     if (!P.in_flight) return P.proved ? 0 : fail(ZKP_HIP_E_ARGUMENT, "batch has not been launched (zkp_hip_batch_prove / _prove_async)");
     HIP_TRY(hipEventSynchronize(P.finished));
-    P.in_flight = false; P.proved = true;
+    P.in_flight = false;
+    if (P.self_check && P.n) { const int rc = self_check_shard(P); if (rc) return rc; }
+    P.proved = true;
     trace_dump();
     return 0;
 }
@@ -517,7 +659,8 @@ void free_shard(ShardPlan& P) {
 
 int batch_stage(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, const uint8_t* seeds, zkp_hip_batch** out) {
     int rc;
-    if ((rc = check_ops(n, ops, lists))) return rc;
+    bool self_check = false;
+    if ((rc = check_ops(n, ops, lists, &self_check))) return rc;
     std::vector<Device*> devs;
     {
         Device* d0 = nullptr;
@@ -527,7 +670,7 @@ int batch_stage(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, const 
     const size_t S = devs.size();
     std::unique_ptr<zkp_hip_batch> owner_of_B(new zkp_hip_batch());          // freed on every early return and on an exception
     zkp_hip_batch* B = owner_of_B.get();
-    B->n = n; B->shards.resize(S);
+    B->n = n; B->self_check = self_check; B->shards.resize(S);
     for (size_t k = 0; k < S; k++) B->shards[k].d = devs[k];
     {
         std::vector<uint32_t> owner(n);
@@ -535,10 +678,35 @@ int batch_stage(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, const 
         for (uint64_t i = 0; i < n; i++) B->shards[owner[i]].gidx.push_back((uint32_t)i);        // ascending op order within a shard
     }
     for (auto& P : B->shards) P.n = (uint32_t)P.gidx.size();
-    rc = for_each_shard(*B, [&](ShardPlan& P) { return stage_shard(P, ops, lists, seeds); });
+    rc = for_each_shard(*B, [&](ShardPlan& P) { return stage_shard(P, ops, lists, seeds, self_check); });
     if (rc < 0) { const std::string keep = t_err; (void)for_each_shard(*B, [&](ShardPlan& P) { free_shard(P); return 0; }, false); return fail(rc, keep); }
     B->max_total = 0; for (auto& P : B->shards) B->max_total += P.max_total;
     *out = owner_of_B.release();
+    return 0;
+}
+
+// ZKP_HIP_SELF_CHECK_FLIP=<global op index>:<byte offset>, read on every prove of a flagged batch: which shard flips which byte of which
+// local op's arena record between proving and verification (a diagnostic: how tests see the self-check refuse something)
+int read_self_check_flip(zkp_hip_batch& B) {
+    for (auto& P : B.shards) P.flip_op = -1;
+    const char* v = getenv("ZKP_HIP_SELF_CHECK_FLIP");
+    if (!v || !*v || !B.self_check) return 0;
+    char* end = nullptr;
+    const bool digit0 = *v >= '0' && *v <= '9';
+    const unsigned long long op = digit0 ? strtoull(v, &end, 10) : 0;
+    const char* q = digit0 && end && *end == ':' ? end + 1 : nullptr;
+    const bool digit1 = q && *q >= '0' && *q <= '9';
+    const unsigned long long byte = digit1 ? strtoull(q, &end, 10) : 0;
+    if (!digit1 || *end) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP must be <op index>:<byte offset>");
+    if (op >= B.n) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the op index is beyond the batch");
+    for (auto& P : B.shards) {
+        const auto it = std::lower_bound(P.gidx.begin(), P.gidx.end(), (uint32_t)op);
+        if (it == P.gidx.end() || *it != (uint32_t)op) continue;
+        const uint32_t j = (uint32_t)(it - P.gidx.begin()), k = P.op_variant[j];
+        if (k == 0) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the op was refused by validation and has no arena record");
+        if (byte >= P.v_stride[k]) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the byte offset is beyond the op's arena record");
+        P.flip_op = j; P.flip_byte = (uint32_t)byte;
+    }
     return 0;
 }
 
@@ -601,9 +769,10 @@ int zkp_hip_process_batch_bytes(uint64_t n, const zkp_hip_op* ops, uint64_t* max
     if (!max_total || (n && !ops)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     uint64_t t = 0;
     for (uint64_t i = 0; i < n; i++) {
-        if (ops[i].kind < ZKP_HIP_OP_RANGE || ops[i].kind > ZKP_HIP_OP_CONSISTENCY) return fail(ZKP_HIP_E_ARGUMENT, "unknown operation kind");
+        if (op_kind(ops[i]) < ZKP_HIP_OP_RANGE || op_kind(ops[i]) > ZKP_HIP_OP_CONSISTENCY) return fail(ZKP_HIP_E_ARGUMENT, "unknown operation kind");
         t += op_max_bytes(ops[i]);
     }
+    { int rcf = self_check_flag(n, ops, nullptr); if (rcf) return rcf; }
     *max_total = t;
     return 0;
 } ZKP_API_CATCH_INT
@@ -618,8 +787,17 @@ int zkp_hip_batch_stage(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists
 
 int zkp_hip_batch_prove_async(zkp_hip_batch* batch) try {
     if (!batch) return fail(ZKP_HIP_E_ARGUMENT, "null batch");
+    if (batch->self_check) {
+        // an earlier prove of this batch that is still running finishes under the switch value read at ITS launch, before this call's is read
+        bool busy = false;
+        for (auto& P : batch->shards) busy = busy || P.in_flight;
+        if (busy) { int rcw = for_each_shard(*batch, [&](ShardPlan& P) { return P.in_flight ? wait_shard(P) : 0; }); if (rcw < 0) return rcw; }
+        int rcf = read_self_check_flip(*batch); if (rcf) return rcf;
+    }
+    batch->proved = false;          // what an earlier prove left is not this prove's result: a fetch after a failed wait fails, it does not return old proofs
     int rc = for_each_shard(*batch, [&](ShardPlan& P) {
         if (P.in_flight) { int rcw = wait_shard(P); if (rcw) return rcw; }          // re-proving a batch that is still running: one at a time per batch
+        P.proved = false;
         return launch_shard(P);
     });
     return rc < 0 ? rc : 0;

@@ -5,9 +5,14 @@ namespace {
 struct VfyState { void* buf = nullptr; size_t cap = 0; LayoutSet set; bool ready = false; };      // per shard (Device::vfy)
 VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy; }
 
-// scheme 1 (range: bounds = mins, maxs; two jobs per envelope), 3 (threshold: bounds = thresholds, maxs unused; one job) or
-// 6 (consistency: no bounds; k - 1 jobs per envelope, counted on the host from each envelope's own k field)
-int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
+// The verifier on device pointers: n envelopes at `stride` bytes in d_proofs, d_lens[i] bytes used, verdicts into d_ok (device); waits for them.
+// scheme 1 (range: bounds = d_mins, d_maxs; two jobs per envelope), 3 (threshold: bounds = thresholds, d_maxs unused; one job) or
+// 6 (consistency: no bounds; job_counts[i] jobs for envelope i, a host array from the caller -- the host entry point counts k - 1 from each
+// envelope's own k field, the batch self-check knows its ops' list lengths; the device step rejects an envelope whose k disagrees).
+// The batch check (k_rlc_*), its fallback and its three switches are in here, so every caller gets the same verdicts.
+// ok_host (may be null): the verdicts are also copied there before the one wait that ends the call.
+int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t stride, const uint32_t* d_lens, const uint64_t* d_mins, const uint64_t* d_maxs, uint8_t* d_ok,
+                     const uint32_t* job_counts, uint8_t* ok_host) {
     int rc;
     if ((rc = ensure_bp())) return rc;
     VfyState& S = vfys();
@@ -19,12 +24,7 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
     std::vector<uint32_t> job_base;
     if (scheme == 6) {
         job_base.resize(n + 1); job_base[0] = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint8_t* env = proofs + stride * i; uint64_t k = 0;
-            if (lens[i] <= stride && lens[i] >= 14) k = (uint64_t)env[10] | ((uint64_t)env[11] << 8) | ((uint64_t)env[12] << 16) | ((uint64_t)env[13] << 24);
-            const bool fits = k >= 1 && k < (1u << 20) && 10 + 4 + 32 * k + (uint64_t)(4 + RP_BYTES + 32) * (k - 1) + 32 <= lens[i];
-            job_base[i + 1] = job_base[i] + (fits ? (uint32_t)(k - 1) : 0u);       // the device step rejects an envelope whose k disagrees
-        }
+        for (uint64_t i = 0; i < n; i++) job_base[i + 1] = job_base[i] + job_counts[i];
     }
     const uint32_t M = scheme == 6 ? job_base[n] : (uint32_t)(jobs_per * n), Mw = M ? M : 1;
     const DevLayout& D = pick_layout(S.set, Mw);
@@ -32,7 +32,7 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
     // workspace
     size_t off = 0;
     auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_in = sz(stride * n), o_len = sz(4 * n), o_min = sz(8 * n), o_max = sz(8 * n), o_ok = sz(n), o_jb = sz(4 * (n + 1)), o_eb = sz(4 * n),
+    const size_t o_jb = sz(4 * (n + 1)), o_eb = sz(4 * n),
                  o_poff = sz(8ull * Mw), o_voff = sz(8ull * Mw), o_kind = sz(Mw), o_lgn = sz(Mw), o_bad = sz(4ull * Mw),
                  o_pts = sz((size_t)VP_NUM * GE_W * 4 * Mw), o_scal = sz((size_t)VS_NUM * 32 * Mw),
                  o_zero0 = off,                                                                   // ---- zero-initialised from here
@@ -57,23 +57,18 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
         HIP_TRY(hipMalloc(&S.buf, off)); S.cap = off;
     }
     uint8_t* base = (uint8_t*)S.buf;
-    HIP_TRY(hipMemcpyAsync(base + o_in, proofs, stride * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(base + o_len, lens, 4 * n, hipMemcpyHostToDevice, st));
-    if (mins) HIP_TRY(hipMemcpyAsync(base + o_min, mins, 8 * n, hipMemcpyHostToDevice, st));
-    if (maxs) HIP_TRY(hipMemcpyAsync(base + o_max, maxs, 8 * n, hipMemcpyHostToDevice, st));
     if (scheme == 6) HIP_TRY(hipMemcpyAsync(base + o_jb, job_base.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));
     const uint16_t tcb[2] = {0, (uint16_t)(D.nchunks + VP_NUM)};       // one target: the fixed chunks and the 17 proof-point products
     HIP_TRY(hipMemcpyAsync(base + o_tcb, tcb, sizeof tcb, hipMemcpyHostToDevice, st));
     VfyView V{};
-    V.M = M; V.in = base + o_in; V.proof_off = (uint64_t*)(base + o_poff); V.venc_off = (uint64_t*)(base + o_voff); V.kind = base + o_kind; V.lgn = base + o_lgn;
+    V.M = M; V.in = d_proofs; V.proof_off = (uint64_t*)(base + o_poff); V.venc_off = (uint64_t*)(base + o_voff); V.kind = base + o_kind; V.lgn = base + o_lgn;
     V.bad = (int32_t*)(base + o_bad); V.pts = (uint32_t*)(base + o_pts); V.scal = (uint32_t*)(base + o_scal); V.digits = (uint32_t*)(base + o_dig);
     V.vscal = (uint32_t*)(base + o_vs); V.partial = (uint32_t*)(base + o_part); V.var_chunk0 = D.nchunks; V.table = dev().d_edg_table; V.wbits = dev().edg.wbits;
     V.job_base = (const uint32_t*)(base + o_jb); V.env_bad = (int32_t*)(base + o_eb);
-    const uint32_t* d_len = (const uint32_t*)(base + o_len);
-    if (scheme == 1) bpv_launch_parse(V, (uint32_t)n, stride, d_len, (const uint64_t*)(base + o_min), (const uint64_t*)(base + o_max), st);
-    else if (scheme == 3) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_len, (const uint64_t*)(base + o_min), st);
-    else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_len, st);
+    if (scheme == 1) bpv_launch_parse(V, (uint32_t)n, stride, d_lens, d_mins, d_maxs, st);
+    else if (scheme == 3) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_lens, d_mins, st);
+    else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_lens, st);
     uint32_t* enc = (uint32_t*)(base + o_enc);
     bool accepted_as_a_batch = false;
     if (M) bpv_launch_decode(V, st);
@@ -130,12 +125,37 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
         launch_sum_ed(R, sums, st);
         k_encode<<<dim3((M + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
     }
-    if (scheme == 6) bpv_launch_final_ranges(V, enc, (uint32_t)n, base + o_ok, st);
-    else bpv_launch_final(V, enc, (uint32_t)n, base + o_ok, jobs_per, st);
+    if (scheme == 6) bpv_launch_final_ranges(V, enc, (uint32_t)n, d_ok, st);
+    else bpv_launch_final(V, enc, (uint32_t)n, d_ok, jobs_per, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ok, base + o_ok, n, hipMemcpyDeviceToHost, st));
+    if (ok_host) HIP_TRY(hipMemcpyAsync(ok_host, d_ok, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+// the host-buffer entry points: upload, then the core above (the consistency job counts are read from the envelopes' own k fields)
+int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
+    std::vector<uint32_t> job_counts;
+    if (scheme == 6) {
+        job_counts.resize(n);
+        for (uint64_t i = 0; i < n; i++) {
+            const uint8_t* env = proofs + stride * i; uint64_t k = 0;
+            if (lens[i] <= stride && lens[i] >= 14) k = (uint64_t)env[10] | ((uint64_t)env[11] << 8) | ((uint64_t)env[12] << 16) | ((uint64_t)env[13] << 24);
+            const bool fits = k >= 1 && k < (1u << 20) && 10 + 4 + 32 * k + (uint64_t)(4 + RP_BYTES + 32) * (k - 1) + 32 <= lens[i];
+            job_counts[i] = fits ? (uint32_t)(k - 1) : 0u;       // the device step rejects an envelope whose k disagrees
+        }
+    }
+    hipStream_t st = dev().stream;
+    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t *d_min = nullptr, *d_max = nullptr;
+    DevScope mem;
+    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_len, 4 * n)); HIP_TRY(mem.alloc(&d_ok, n));
+    if (mins) HIP_TRY(mem.alloc(&d_min, 8 * n));
+    if (maxs) HIP_TRY(mem.alloc(&d_max, 8 * n));
+    HIP_TRY(hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st));
+    if (mins) HIP_TRY(hipMemcpyAsync(d_min, mins, 8 * n, hipMemcpyHostToDevice, st));
+    if (maxs) HIP_TRY(hipMemcpyAsync(d_max, maxs, 8 * n, hipMemcpyHostToDevice, st));
+    return verify_bp_device(scheme, n, d_in, stride, d_len, d_min, d_max, d_ok, job_counts.data(), ok);
 }
 
 void bpv_release_all() {

@@ -762,21 +762,16 @@ int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, cons
     return 0;
 }
 
-// Verdicts of n envelopes: one weighted pairing check for a large batch (g16_rlc.h); when it does not stand, the localisation pass and the
-// per-envelope check of the suspect envelopes, or of all of them.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test knob) takes the lane-per-chain
-// kernels for everything.
-int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
+// Verdicts of n envelopes that lie in device memory (d_in, `stride` bytes each, d_len[i] bytes used) into d_ok (device) and ok (host, n bytes:
+// the localisation pass reads the batch check's verdicts there): one weighted pairing check for a large batch (g16_rlc.h); when it does not
+// stand, the localisation pass and the per-envelope check of the suspect envelopes, or of all of them.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test
+// knob) takes the lane-per-chain kernels for everything.  `mem` owns the scratch and `e` is the state of the caller's earlier asynchronous calls
+// on the shard's stream.  The chains run on side streams against that scratch: after a failure (a non-zero return) the caller waits for the
+// whole device before `mem` hands its blocks back (Quiesce in verify_g16_host).
+int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint8_t* d_ok, uint8_t* ok, DevScope& mem, hipError_t e) {
     G16Key& K = g16s().key[kind];
     if (!K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
     hipStream_t st = dev().stream;
-    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr;
-    DevScope mem;
-    // Chain B and the subgroup chain of the Fq2 machine run on the tables' side streams against d_scratch; DevScope only quiesces the
-    // shard's main stream, so every early return below first waits for the whole device before the blocks go back to the pool.
-    struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;
-    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_ok, n)); HIP_TRY(mem.alloc(&d_len, 4 * n));
-    hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
     static const int use_vm = env_int("ZKP_HIP_G16_VERIFY_VM", 1);
     std::unique_ptr<G16VerifyTally> tally;          // set once a batch check has not stood
     if (use_vm) {
@@ -805,7 +800,7 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
             if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
-            if (counters[0] == 0 && counters[1] == 0 && counters[2] == 0 && counters[3] == 1) { quiesce.armed = false; return 0; }
+            if (counters[0] == 0 && counters[1] == 0 && counters[2] == 0 && counters[3] == 1) return 0;
             if (getenv("ZKP_HIP_G16_BATCH_VERIFY_ONLY")) {          // diagnostic (tests): say that the batch check did not stand instead of verifying again
                 char msg[160]; snprintf(msg, sizeof msg, "the batch check did not stand (special %u, outside the subgroup %u, anomalies %u, product is one: %u)", counters[0], counters[1], counters[2], counters[3]);
                 return fail(ZKP_HIP_E_RUNTIME, msg);
@@ -814,11 +809,26 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
             bool done = false;
             const int rc = localise_g16(kind, K, d_in, stride, d_len, (uint32_t)n, d_rlc, d_ok, ok, counters, mem, *tally, &done);
             if (rc) return rc;
-            if (done) { quiesce.armed = false; return 0; }
+            if (done) return 0;
             tally->envelopes += n;
         }
     }
-    const int rc = verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem, e);
+    return verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem, e);
+}
+
+// the host-buffer entry points: upload, then the core above
+int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
+    if (!g16s().key[kind].vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
+    hipStream_t st = dev().stream;
+    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr;
+    DevScope mem;
+    // Chain B and the subgroup chain of the Fq2 machine run on the tables' side streams against d_scratch; DevScope only quiesces the
+    // shard's main stream, so every early return below first waits for the whole device before the blocks go back to the pool.
+    struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;
+    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_ok, n)); HIP_TRY(mem.alloc(&d_len, 4 * n));
+    hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
+    const int rc = verify_g16_core(kind, n, d_in, stride, d_len, d_ok, ok, mem, e);
     if (rc) return rc;
     quiesce.armed = false;
     return 0;

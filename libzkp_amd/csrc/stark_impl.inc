@@ -17,6 +17,16 @@ int ensure_stark_constants() {
     return 0;
 }
 
+// The verifier on device pointers: n envelopes at `stride` bytes in d_in, d_len[i] bytes used, verdicts into d_ok (device), enqueued on the
+// shard's stream (the host-buffer entry point uploads and calls this; the batch self-check calls it on the arena's rows)
+int verify_stark_device(uint64_t n, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, const uint64_t* d_old, uint8_t* d_ok) {
+    int rc = ensure_stark_constants();
+    if (rc) return rc;
+    stark_launch_verify(d_in, stride, d_len, d_old, (uint32_t)n, g_stark_const, d_ok, dev().stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 void stark_release_all() {
     if (!dev().stark) return;
     if (dev().stark->consts) (void)hipFree(dev().stark->consts);
@@ -80,7 +90,7 @@ int zkp_hip_verify_improvement_batch(uint64_t n, const uint8_t* proofs, uint64_t
     hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_old, old_values, 8 * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { stark_launch_verify(d_in, stride, d_len, d_old, (uint32_t)n, g_stark_const, d_ok, st); e = hipGetLastError(); }
+    if (e == hipSuccess && (rc = verify_stark_device(n, d_in, stride, d_len, d_old, d_ok))) return rc;
     if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));

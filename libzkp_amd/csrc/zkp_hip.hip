@@ -35,6 +35,7 @@
 #include "stark_launch.h"
 #include "bpv_launch.h"
 #include "edg_launch.h"
+#include "batch_self_check.h"
 #include "../../include/libzkp_hip.h"
 
 // ================================================================================================ kernels
@@ -334,6 +335,8 @@ struct Device {
     KProf prof[3];                      // ZKP_HIP_KERNEL_MSM_ED25519 / _BN254_G1 / _BN254_G2
     // ZKP_HIP_COUNTER_G16_VERIFY, always counted: what the Groth16 verifier did after batch checks that did not stand (g16_impl.inc: G16VerifyTally)
     struct G16VerifyStats { double ms = 0; uint64_t launches = 0, adds = 0; } g16_verify;
+    // ZKP_HIP_COUNTER_BATCH_SELF_CHECK, always counted: ops verified / refused by the self-check of flagged batches, host ms from the end of proving (batch_impl.inc: self_check_shard)
+    struct SelfCheckStats { double ms = 0; uint64_t verified = 0, refused = 0; } self_check;
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
 };
@@ -1228,6 +1231,7 @@ void zkp_hip_shutdown(void) try {
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
         d->g16_verify = Device::G16VerifyStats();
+        d->self_check = Device::SelfCheckStats();
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
@@ -1242,7 +1246,7 @@ void zkp_hip_profile_enable(int on) try {
 
 // accumulated over all shards
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset) try {
-    if (which < 0 || which > ZKP_HIP_COUNTER_G16_VERIFY) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
+    if (which < 0 || which > ZKP_HIP_COUNTER_BATCH_SELF_CHECK) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
@@ -1252,6 +1256,13 @@ int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint6
             Device::G16VerifyStats& V = d->g16_verify;
             tms += V.ms; tl += V.launches; ta += V.adds;
             if (reset) V = Device::G16VerifyStats();
+            continue;
+        }
+        if (which == ZKP_HIP_COUNTER_BATCH_SELF_CHECK) {
+            std::lock_guard<std::mutex> dl(d->mu);
+            Device::SelfCheckStats& V = d->self_check;
+            tms += V.ms; tl += V.verified; ta += V.refused;
+            if (reset) V = Device::SelfCheckStats();
             continue;
         }
         Bind bind; int rc = bind.open(d);

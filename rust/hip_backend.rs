@@ -198,14 +198,17 @@ pub fn init_all_gpus(n_gpus: u32) -> ZkpResult<()> {
 
 /// Replacement of the rayon map in advanced::process_batch (advanced/batch.rs:123-131): one FFI call for the whole
 /// batch; order of results = order of `batch_add_*`; any failed op fails the batch (collect::<ZkpResult<_>>).
-pub fn process_batch_operations(ops: &[BatchOperation]) -> ZkpResult<Vec<Vec<u8>>> {
+/// `self_check`: every proof is verified on the GPU against its own op before the batch is released (`ZKP_HIP_OP_SELF_CHECK`);
+/// same proof bytes, and an op whose proof is refused fails the batch as ProofGenerationFailed.
+pub fn process_batch_operations(ops: &[BatchOperation], self_check: bool) -> ZkpResult<Vec<Vec<u8>>> {
     let mut lists: Vec<u64> = Vec::new();
     let mut list = |v: &Vec<u64>| {
         let off = lists.len() as u64;
         lists.extend_from_slice(v);
         (v.len() as u32, off)
     };
-    let raw: Vec<ffi::zkp_hip_op> = ops
+    let flag = if self_check { ffi::OP_SELF_CHECK } else { 0 };
+    let mut raw: Vec<ffi::zkp_hip_op> = ops
         .iter()
         .map(|op| match op {
             BatchOperation::RangeProof { value, min, max } => ffi::zkp_hip_op { kind: ffi::OP_RANGE, count: 0, a: *value, b: *min, c: *max, list_off: 0 },
@@ -225,6 +228,9 @@ pub fn process_batch_operations(ops: &[BatchOperation]) -> ZkpResult<Vec<Vec<u8>
             }
         })
         .collect();
+    for op in raw.iter_mut() {
+        op.kind |= flag; // a property of the whole batch: on every op or on none
+    }
     let n = raw.len();
     if n == 0 {
         return Ok(vec![]);

@@ -22,9 +22,14 @@ pub const OP_THRESHOLD: u32 = 3;
 pub const OP_MEMBERSHIP: u32 = 4;
 pub const OP_IMPROVEMENT: u32 = 5;
 pub const OP_CONSISTENCY: u32 = 6;
+/// `ZKP_HIP_OP_SELF_CHECK`: OR-ed into `kind` of every op of a call; the batch's proofs are verified on the GPU against their own ops
+/// before they are released, and a refused op fails with status 2 (ProofGenerationFailed).
+pub const OP_SELF_CHECK: u32 = 0x100;
 
 /// `zkp_hip_profile_read_kernel` id (not a kernel): segment checks run / envelopes verified again / host ms after Groth16 batch checks that did not stand.
 pub const ZKP_HIP_COUNTER_G16_VERIFY: c_int = 3;
+/// `zkp_hip_profile_read_kernel` id (not a kernel): ops verified / ops refused / host ms of the self-check of flagged batches.
+pub const ZKP_HIP_COUNTER_BATCH_SELF_CHECK: c_int = 4;
 
 /// `zkp_hip_op`: one BatchOperation (utils/composition.rs:343-350) flattened; `kind` = the envelope scheme id.
 #[repr(C)]
