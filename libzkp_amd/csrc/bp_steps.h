@@ -213,9 +213,13 @@ struct ReduceView {
     const uint64_t* out_off;             // optional [rows]: also write target 0's 32 bytes to out + out_off[row]
     uint8_t* out;
     const uint32_t* corr;                // optional [ntargets][ACC_W]: point added to each target's sum (-(#chunks) * offset)
+    // optional [ntargets]: target t sums the chunks [target_chunk_begin[t], target_chunk_end[t]) instead of ending where target t + 1
+    // begins, so that the ranges of two targets may overlap (the Groth16 A / B1 launch, g16_share.h).  nullptr: the ranges tile the chunks
+    const uint16_t* target_chunk_end = nullptr;
 };
+ZKP_HD inline uint32_t reduce_chunk_end(const ReduceView& r, uint32_t target) { return r.target_chunk_end ? r.target_chunk_end[target] : r.target_chunk_begin[target + 1]; }
 ZKP_HD inline void reduce_encode_thread(const ReduceView& r, uint32_t target, uint32_t row) {
-    const uint32_t c0 = r.target_chunk_begin[target], c1 = r.target_chunk_begin[target + 1];
+    const uint32_t c0 = r.target_chunk_begin[target], c1 = reduce_chunk_end(r, target);
     ge acc = ld_ge(r.partial, c0, row, r.rows);
     for (uint32_t c = c0 + 1; c < c1; c++) acc = ge_add(acc, ld_ge(r.partial, c, row, r.rows));
     sc e; ge_ristretto_encode(e.v, acc);

@@ -16,7 +16,7 @@ struct G16Key {
     uint64_t table_bytes = 0;                           // HBM held by this key's two MSM tables (shared by the shards of one GPU)
     // chunkings of the two key-point MSMs, built on demand per chunk count (the grid is matched to the batch size at run time)
     struct Chunking { DevLayout lay; const uint32_t* corr = nullptr; const uint16_t* scal = nullptr; };   // scal: digit row of each slot of this layout
-    std::vector<SlotList> targets_g1, targets_g2;
+    std::vector<SlotList> targets_g1, targets_g2;              // G1: A' | S (the slots A and B1 share, g16_share.h; may be empty) | B1' | C
     std::vector<uint16_t> hscal_g1, hscal_g2;  // digit row per key point (host copy; the layouts carry their own device copy)
     std::map<uint64_t, Chunking> lays_g1, lays_g2;            // key = part << 32 | chunk count
     uint64_t win_g1 = 0, win_g2 = 0;          // windows (= mixed additions) per proof
@@ -124,14 +124,16 @@ uint32_t choose_chunks(uint64_t windows, uint32_t ntargets, uint32_t rows, uint3
 }
 // `part` selects the targets of the launch: G16_PART_ALL (G2), or for G1 the two launches of the split pipeline (run_g16):
 // G16_PART_AB = A and B1 (scalars z only, ready after the witness step), G16_PART_C = the l / h sum (needs the QAP step).
+// The A / B1 launch of a key with shared points has three slot lists A' | S | B1' and still two sums, over the overlapping chunk
+// ranges A' u S and S u B1' (g16_share.h); a chunking of that form has three targets.
 enum { G16_PART_ALL = 0, G16_PART_AB = 1, G16_PART_C = 2 };
 int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chunking** out) {
     const uint32_t resident = (uint32_t)dev().num_cu * g16_msm_blocks_per_cu(g2);      // workgroups the chip holds at a time
     const auto& all = g2 ? K.targets_g2 : K.targets_g1;
     std::vector<SlotList> targets;
-    if (part == G16_PART_ALL) targets = all;
-    else if (part == G16_PART_AB) targets.assign(all.begin(), all.begin() + 2);
-    else targets.assign(all.begin() + 2, all.end());
+    if (part == G16_PART_ALL) { if (!g2) return fail(ZKP_HIP_E_ARGUMENT, "G16_PART_ALL is the G2 launch"); targets = all; }     // (targets_g1 may hold an empty S: no layout target)
+    else if (part == G16_PART_AB) targets = g16_ab_targets(all[0], all[1], all[2]);
+    else targets.assign(all.begin() + 3, all.end());
     uint64_t windows = 0; for (auto& t : targets) for (auto& sl : t) windows += sl.second;
     uint32_t c = choose_chunks(windows, (uint32_t)targets.size(), rows, resident, g16_msm_rows_per_block(g2));
     if (g_budget_request >= 10000) c = g_budget_request - 10000;                  // benchmarking knob
@@ -146,8 +148,10 @@ int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chun
         const GatherShape shape{K.rx.nent, K.rx.slot_ent, K.rx.uneven ? 1u : 0u, K.rx.digw};
         if ((rc = upload_layout(ch.lay, L, &shape, scal.data()))) return rc;
         std::vector<uint32_t> corr;
-        for (uint32_t t = 0; t < L.ntargets(); t++) {
-            const uint32_t k = L.target_chunk_begin[t + 1] - L.target_chunk_begin[t];
+        const bool ab3 = part == G16_PART_AB && L.ntargets() == 3;      // A' | S | B1': two sums, over the ranges g16_ab_ranges names
+        const G16AbRanges ab = ab3 ? g16_ab_ranges(L) : G16AbRanges{};
+        for (uint32_t t = 0; t < (ab3 ? 2u : L.ntargets()); t++) {       // every chunk of a sum's own range started from O
+            const uint32_t k = ab3 ? ab.end[t] - ab.begin[t] : L.target_chunk_begin[t + 1] - L.target_chunk_begin[t];
             if (!g2) append_words(corr, host_neg_multiple(g_off.o1, k)); else append_words(corr, host_neg_multiple(g_off.o2, k));
         }
         if ((rc = dev_upload(K, &ch.corr, corr))) return rc;
@@ -199,7 +203,7 @@ int choose_radix(size_t n1, size_t n2, uint32_t* wbits_out, bool* uneven_out) {
 }
 // One table set per (GPU, circuit, key bytes, radix) in the process: the shards registered on the same HIP device (zkp_hip_init_devices
 // with a device listed twice, as the one-GPU tests do; several contexts of a server) share it instead of holding ~65 GB each.
-struct SharedTables { int hip_dev, kind; uint8_t digest[32]; uint32_t wbits; uint32_t *g1, *g2; int refs; };      // wbits | uneven << 8
+struct SharedTables { int hip_dev, kind; uint8_t digest[32]; uint32_t wbits; bool share_ab; uint32_t *g1, *g2; int refs; };      // wbits | uneven << 8; share_ab: laid out with the shared A / B1 slots (g16_share.h)
 struct TableRegistry { std::mutex mu; std::vector<SharedTables> v; std::map<int, std::unique_ptr<std::mutex>> build_mu; };
 TableRegistry& table_registry() { static TableRegistry* r = new TableRegistry(); return *r; }
 void release_shared_tables(G16Key& K) {
@@ -317,10 +321,15 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     if (alpha_g1.inf || beta_g1.inf || delta_g1.inf || beta_g2.inf || delta_g2.inf) return fail(ZKP_HIP_E_ARGUMENT, "degenerate proving key");
     // scalar rows: z_k (nv) | h_i (m-1) | r | s | -rs | one
     const uint32_t SC_H = K.nv, SC_R = K.nv + K.m - 1, SC_S = SC_R + 1, SC_NRS = SC_R + 2, SC_ONE = SC_R + 3;
-    // the radix of this key's tables (the point counts are known from the file's vector lengths: a, b1, l, h + delta x3, alpha, beta | b2 + delta, beta)
+    // the radix of this key's tables (the point counts are known from the file's vector lengths: a, b1 less the points they share, l, h + delta x3, alpha, beta | b2 + delta, beta)
     // If another shard of this GPU already holds tables for these key bytes, this shard takes a reference AND their radix (what is free
     // now -- less than when the first shard chose -- must not pick a smaller one and build a second set); choose_radix only when building.
     // One load at a time per GPU from here to the registration of freshly built tables.
+    // The slot lists of A and B1, from the key's points alone.  ZKP_HIP_G16_SHARE_AB=0 gives every finite b_g1_query point its own slot
+    // and table again; it is read here, once per load, and tables are shared only between loads that read the same value.
+    const bool share_ab = env_int("ZKP_HIP_G16_SHARE_AB", 1) != 0;
+    std::vector<uint8_t> var_class(cs.inst_nwin); var_class.insert(var_class.end(), cs.wit_nwin.begin(), cs.wit_nwin.end());
+    const G16AbSlots ab = g16_ab_slots(aq, b1q, var_class, share_ab);
     uint8_t digest[32]; sha256_host(digest, pk, len);
     TableRegistry& TR = table_registry();
     std::mutex* bm = nullptr;
@@ -332,20 +341,20 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         {
             std::lock_guard<std::mutex> lk(TR.mu);
             for (size_t i = 0; i < TR.v.size() && !forced; i++)
-                if (TR.v[i].refs > 0 && TR.v[i].hip_dev == dev().hip_dev && TR.v[i].kind == kind && !memcmp(TR.v[i].digest, digest, 32)) {
+                if (TR.v[i].refs > 0 && TR.v[i].hip_dev == dev().hip_dev && TR.v[i].kind == kind && TR.v[i].share_ab == share_ab && !memcmp(TR.v[i].digest, digest, 32)) {
                     found = (int)i; TR.v[i].refs++; wb = TR.v[i].wbits & 0xffu; uneven = (TR.v[i].wbits >> 8) != 0;
                     K.shared_tables = found; K.table_g1 = TR.v[i].g1; K.table_g2 = TR.v[i].g2;
                     break;
                 }
         }
-        if (found < 0 && (rc = choose_radix(aq.size() + b1q.size() + lq.size() + hq.size() + 5, b2q.size() + 2, &wb, &uneven))) return rc;
+        if (found < 0 && (rc = choose_radix(aq.size() + b1q.size() - ab.s.size() + lq.size() + hq.size() + 5, b2q.size() + 2, &wb, &uneven))) return rc;
         K.rx = g16_radix(wb, uneven);
     }
     const uint32_t NWIN = K.rx.nwin;
     auto var_nwin = [&](uint32_t k) -> uint8_t { return g16_class_nwin(k < cs.n_inst ? cs.inst_nwin[k] : cs.wit_nwin[k - cs.n_inst], K.rx); };
     std::vector<g1_aff> bases1; std::vector<g2_aff> bases2;
     std::vector<uint16_t> scal1, scal2;
-    std::vector<SlotList> t1(3), t2(1);
+    std::vector<SlotList> t1(4), t2(1);               // G1: A' | S | B1' | C
     auto add1 = [&](int target, const G1Pt& pt, uint32_t scal, uint8_t nwin) {
         if (pt.inf) return;
         t1[target].push_back({(uint16_t)bases1.size(), nwin}); bases1.push_back(pt.p); scal1.push_back((uint16_t)scal);
@@ -356,13 +365,15 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     };
     if (K.nv + K.m + 3 > 65535 || 3ull * K.nv + K.m + 8 > 65535) return fail(ZKP_HIP_E_UNSUPPORTED, "circuit too large for 16-bit slot indices");
     // A = alpha + sum z_k a_k + r delta ; B = beta + sum z_k b_k + s delta ; Cp = sum aux_k l_k + sum h_i H_i - rs delta
-    for (uint32_t k = 0; k < K.nv; k++) add1(0, aq[k], k, var_nwin(k));
+    // (a variable whose a_query and b_g1_query points are one point has its slot in S, once, and no b_g1_query table: g16_share.h)
+    for (auto& sl : ab.a) add1(0, aq[sl.first], sl.first, var_nwin(sl.first));
     add1(0, delta_g1, SC_R, NWIN); add1(0, alpha_g1, SC_ONE, 1);
-    for (uint32_t k = 0; k < K.nv; k++) add1(1, b1q[k], k, var_nwin(k));
-    add1(1, delta_g1, SC_S, NWIN); add1(1, beta_g1, SC_ONE, 1);
-    for (uint32_t k = 0; k < K.n_wit; k++) add1(2, lq[k], K.n_inst + k, var_nwin(K.n_inst + k));
-    for (uint32_t i = 0; i + 1 < K.m; i++) add1(2, hq[i], SC_H + i, NWIN);
-    add1(2, delta_g1, SC_NRS, NWIN);
+    for (auto& sl : ab.s) add1(1, aq[sl.first], sl.first, var_nwin(sl.first));
+    for (auto& sl : ab.b) add1(2, b1q[sl.first], sl.first, var_nwin(sl.first));
+    add1(2, delta_g1, SC_S, NWIN); add1(2, beta_g1, SC_ONE, 1);
+    for (uint32_t k = 0; k < K.n_wit; k++) add1(3, lq[k], K.n_inst + k, var_nwin(K.n_inst + k));
+    for (uint32_t i = 0; i + 1 < K.m; i++) add1(3, hq[i], SC_H + i, NWIN);
+    add1(3, delta_g1, SC_NRS, NWIN);
     for (uint32_t k = 0; k < K.nv; k++) add2(b2q[k], k, var_nwin(k));
     add2(delta_g2, SC_S, NWIN); add2(beta_g2, SC_ONE, 1);
     // make_layout keeps insertion order, so slot s of the layout <-> entry s of bases/scal when targets are laid out in order
@@ -383,14 +394,14 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         {
             std::lock_guard<std::mutex> lk(R.mu);         // (a forced radix skipped the adoption above: an entry of exactly that radix is still shared)
             for (size_t i = 0; i < R.v.size(); i++)
-                if (R.v[i].refs > 0 && R.v[i].hip_dev == dev().hip_dev && R.v[i].kind == kind && R.v[i].wbits == (K.rx.wbits | K.rx.uneven << 8) && !memcmp(R.v[i].digest, digest, 32)) { found = (int)i; R.v[i].refs++; break; }
+                if (R.v[i].refs > 0 && R.v[i].hip_dev == dev().hip_dev && R.v[i].kind == kind && R.v[i].wbits == (K.rx.wbits | K.rx.uneven << 8) && R.v[i].share_ab == share_ab && !memcmp(R.v[i].digest, digest, 32)) { found = (int)i; R.v[i].refs++; break; }
         }
         if (found < 0) {
             uint32_t *t1 = nullptr, *t2 = nullptr;
             if ((rc = build_tables<20>(K, bases1, &t1, true, K.rx, false))) return rc;
             if ((rc = build_tables<40>(K, bases2, &t2, true, K.rx, false))) { (void)hipFree(t1); return rc; }
             std::lock_guard<std::mutex> lk(R.mu);
-            SharedTables e{}; e.hip_dev = dev().hip_dev; e.kind = kind; memcpy(e.digest, digest, 32); e.wbits = K.rx.wbits | K.rx.uneven << 8; e.g1 = t1; e.g2 = t2; e.refs = 1;
+            SharedTables e{}; e.hip_dev = dev().hip_dev; e.kind = kind; memcpy(e.digest, digest, 32); e.wbits = K.rx.wbits | K.rx.uneven << 8; e.share_ab = share_ab; e.g1 = t1; e.g2 = t2; e.refs = 1;
             R.v.push_back(e); found = (int)R.v.size() - 1;
         }
         std::lock_guard<std::mutex> lk(R.mu);
@@ -599,6 +610,8 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
     // st: A and B1, whose sums the scalar multiplications on side2 wait for, then B2
     if ((rc = launch_msm_key(false, K.rx, *c1, K.table_g1, K.init_g1, rows, V.sdig, p1, st))) return rc;
     ReduceView Rab{}; Rab.rows = rows; Rab.ntargets = 2; Rab.partial = p1; Rab.target_chunk_begin = c1->lay.target_chunk_begin; Rab.corr = c1->corr;
+    // three slot lists A' | S | B1': A sums the chunks [begin[0], begin[2]), B1 the chunks [begin[1], begin[3]) -- S's chunks go into both
+    if (c1->lay.ntargets == 3) Rab.target_chunk_end = c1->lay.target_chunk_begin + 2;
     // The partial sums of A / B1 feed only the scalar multiplications: they go to side2 with them, so that the G2 MSM -- which needs
     // neither -- follows the G1 MSM directly instead of queueing behind a latency-bound kernel that waits for registers beside the other
     // streams' gather waves (traced: 0.8-3.9 ms for a 0.2 ms kernel).

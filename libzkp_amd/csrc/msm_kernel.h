@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(NTHREADS, MIN_WAVES) k_sum_t(ReduceView R, uin
     const uint32_t rl = threadIdx.x % ROWS, slice = threadIdx.x / ROWS;
     const uint32_t row = blockIdx.x * ROWS + rl, target = blockIdx.y;
     const bool active = row < R.rows;
-    const uint32_t c0 = R.target_chunk_begin[target], c1 = R.target_chunk_begin[target + 1];
+    const uint32_t c0 = R.target_chunk_begin[target], c1 = reduce_chunk_end(R, target);
     typename T::Acc acc = T::identity();
     bool have = false;
     if (active) {

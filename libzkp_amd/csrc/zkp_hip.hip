@@ -29,6 +29,7 @@
 #include "sha256_host.h"
 #include "g16_circuit.h"
 #include "g16_keyblob.h"
+#include "g16_share.h"
 #include "msm_kernel.h"
 #include "g16_launch.h"
 #include "g16_verify_launch.h"
