@@ -112,10 +112,11 @@ struct HostCircuitTables {
     std::vector<uint32_t> ptr[3], col[3], coef[3];
     std::vector<uint32_t> tw, tw_inv, coset, coset_inv, zinv;
 };
+inline uint32_t g16_domain_log2(const HostR1CS& cs) { uint32_t lg = 0; while ((1u << lg) < cs.rows.size() + cs.n_inst) lg++; return lg; }      // m = 2^lg holds the rows and one row per instance variable
 inline HostCircuitTables build_circuit_tables(const HostR1CS& cs) {
     HostCircuitTables T;
     T.n_inst = cs.n_inst; T.n_wit = cs.n_wit; T.nv = cs.n_inst + cs.n_wit; T.n_rows = (uint32_t)cs.rows.size();
-    uint32_t m = 1, lg = 0; while (m < T.n_rows + T.n_inst) { m <<= 1; lg++; }
+    const uint32_t lg = g16_domain_log2(cs), m = 1u << lg;
     T.m = m; T.logm = lg;
     auto colidx = [&](uint32_t v) { return (v & WIT) ? cs.n_inst + (v & ~WIT) : v; };
     for (int q = 0; q < 3; q++) {

@@ -84,30 +84,26 @@ g2_aff host_g2_generator() {
     return g2_aff{fq2{c[0], c[1]}, fq2{c[2], c[3]}};
 }
 g1_aff host_g1_generator() { return g1_aff{fq_from_u64(1), fq_from_u64(2)}; }
-struct MsmOffsets { g1_jac o1; g2_jac o2; bool ready = false; };
-MsmOffsets g_off;               // host-side constants, computed once per process
-std::once_flag g_off_once;
-void compute_offsets();
-void ensure_offsets() { std::call_once(g_off_once, compute_offsets); }
-void compute_offsets() {
-    uint8_t h[32]; const char* tag = "libzkp-amd msm offset"; sha256_host(h, (const uint8_t*)tag, strlen(tag));
-    uint32_t k[8]; memcpy(k, h, 32); k[7] &= 0x0fffffffu;
-    g_off.o1 = jac_mul_raw(jac_from_aff(host_g1_generator()), k);
-    g_off.o2 = jac_mul_raw(jac_from_aff(host_g2_generator()), k);
-    g_off.ready = true;
+struct MsmOffsets { g1_jac o1; g2_jac o2; };
+const MsmOffsets& msm_offsets() {               // host-side constants, computed once per process
+    static const MsmOffsets off = [] {
+        uint8_t h[32]; const char* tag = "libzkp-amd msm offset"; sha256_host(h, (const uint8_t*)tag, strlen(tag));
+        uint32_t k[8]; memcpy(k, h, 32); k[7] &= 0x0fffffffu;
+        return MsmOffsets{jac_mul_raw(jac_from_aff(host_g1_generator()), k), jac_mul_raw(jac_from_aff(host_g2_generator()), k)};
+    }();
+    return off;
 }
+template <class J> void append_words(std::vector<uint32_t>& v, const J& p) { const uint32_t* w = reinterpret_cast<const uint32_t*>(&p); for (size_t i = 0; i < sizeof(J) / 4; i++) v.push_back(w[i]); }
 template <class J> J host_neg_multiple(const J& o, uint32_t k) {     // -(k * O), k small
     J acc = o; for (uint32_t i = 1; i < k; i++) acc = jac_add(acc, o);
     return jac_neg(acc);
 }
-template <class J> void append_words(std::vector<uint32_t>& v, const J& p) { const uint32_t* w = reinterpret_cast<const uint32_t*>(&p); for (size_t i = 0; i < sizeof(J) / 4; i++) v.push_back(w[i]); }
-// device copy of O (the accumulator every chunk starts from)
-int upload_offset_point(G16Key& K, bool g2, const uint32_t** d_init) {
-    ensure_offsets();
-    std::vector<uint32_t> init;
-    if (!g2) append_words(init, g_off.o1); else append_words(init, g_off.o2);
-    return dev_upload(K, d_init, init);
+// the words of O (k = 0: the accumulator every chunk starts from) or of -(k O) (what the sum of k chunks is corrected by)
+void append_offset(std::vector<uint32_t>& v, bool g2, uint32_t k) {
+    const MsmOffsets& o = msm_offsets();
+    if (!g2) append_words(v, k ? host_neg_multiple(o.o1, k) : o.o1); else append_words(v, k ? host_neg_multiple(o.o2, k) : o.o2);
 }
+int upload_offset_point(G16Key& K, bool g2, const uint32_t** d_init) { std::vector<uint32_t> init; append_offset(init, g2, 0); return dev_upload(K, d_init, init); }
 // Chunking of one key-point MSM for a batch of `rows` proofs.  One workgroup (G1: 1024 lanes, G2: 512) fills a CU, so the
 // grid runs in strict rounds of `resident` equal workgroups: take the window-granular chunk count that minimises
 // rounds x (windows per workgroup + per-workgroup overhead) + the partial-sum work that grows with the chunk count.
@@ -122,40 +118,25 @@ uint32_t choose_chunks(uint64_t windows, uint32_t ntargets, uint32_t rows, uint3
     }
     return best;
 }
-// `part` selects the targets of the launch: G16_PART_ALL (G2), or for G1 the two launches of the split pipeline (run_g16):
-// G16_PART_AB = A and B1 (scalars z only, ready after the witness step), G16_PART_C = the l / h sum (needs the QAP step).
-// The A / B1 launch of a key with shared points has three slot lists A' | S | B1' and still two sums, over the overlapping chunk
-// ranges A' u S and S u B1' (g16_share.h); a chunking of that form has three targets.
-enum { G16_PART_ALL = 0, G16_PART_AB = 1, G16_PART_C = 2 };
+// (the parts, the layout, the digit rows and the offset counts of a chunking: g16_share.h)
 int get_chunking(G16Key& K, bool g2, int part, uint32_t rows, const G16Key::Chunking** out) {
     const uint32_t resident = (uint32_t)dev().num_cu * g16_msm_blocks_per_cu(g2);      // workgroups the chip holds at a time
-    const auto& all = g2 ? K.targets_g2 : K.targets_g1;
-    std::vector<SlotList> targets;
-    if (part == G16_PART_ALL) { if (!g2) return fail(ZKP_HIP_E_ARGUMENT, "G16_PART_ALL is the G2 launch"); targets = all; }     // (targets_g1 may hold an empty S: no layout target)
-    else if (part == G16_PART_AB) targets = g16_ab_targets(all[0], all[1], all[2]);
-    else targets.assign(all.begin() + 3, all.end());
-    uint64_t windows = 0; for (auto& t : targets) for (auto& sl : t) windows += sl.second;
-    uint32_t c = choose_chunks(windows, (uint32_t)targets.size(), rows, resident, g16_msm_rows_per_block(g2));
+    if (part == G16_PART_ALL && !g2) return fail(ZKP_HIP_E_ARGUMENT, "G16_PART_ALL is the G2 launch");
+    const std::vector<SlotList> targets = g16_part_targets(g2 ? K.targets_g2 : K.targets_g1, part);
+    uint32_t c = choose_chunks(g16_windows(targets), (uint32_t)targets.size(), rows, resident, g16_msm_rows_per_block(g2));
     if (g_budget_request >= 10000) c = g_budget_request - 10000;                  // benchmarking knob
     auto& cache = g2 ? K.lays_g2 : K.lays_g1;
     const uint64_t key = (uint64_t)part << 32 | c;
     auto it = cache.find(key);
     if (it == cache.end()) {
-        const MsmLayout L = make_layout_even(targets, c);
+        const G16Chunks P = g16_plan_chunks(targets, g2 ? K.hscal_g2 : K.hscal_g1, part, c);
         G16Key::Chunking ch; int rc;
-        const auto& hs = g2 ? K.hscal_g2 : K.hscal_g1;
-        std::vector<uint16_t> scal; for (uint16_t b : L.slot_base) scal.push_back(hs[b]);
         const GatherShape shape{K.rx.nent, K.rx.slot_ent, K.rx.uneven ? 1u : 0u, K.rx.digw};
-        if ((rc = upload_layout(ch.lay, L, &shape, scal.data()))) return rc;
+        if ((rc = upload_layout(ch.lay, P.L, &shape, P.scal.data()))) return rc;
         std::vector<uint32_t> corr;
-        const bool ab3 = part == G16_PART_AB && L.ntargets() == 3;      // A' | S | B1': two sums, over the ranges g16_ab_ranges names
-        const G16AbRanges ab = ab3 ? g16_ab_ranges(L) : G16AbRanges{};
-        for (uint32_t t = 0; t < (ab3 ? 2u : L.ntargets()); t++) {       // every chunk of a sum's own range started from O
-            const uint32_t k = ab3 ? ab.end[t] - ab.begin[t] : L.target_chunk_begin[t + 1] - L.target_chunk_begin[t];
-            if (!g2) append_words(corr, host_neg_multiple(g_off.o1, k)); else append_words(corr, host_neg_multiple(g_off.o2, k));
-        }
+        for (uint32_t k : P.offsets) append_offset(corr, g2, k);
         if ((rc = dev_upload(K, &ch.corr, corr))) return rc;
-        if ((rc = dev_upload(K, &ch.scal, scal))) return rc;
+        if ((rc = dev_upload(K, &ch.scal, P.scal))) return rc;
         it = cache.emplace(key, ch).first;
     }
     *out = &it->second;
@@ -204,17 +185,28 @@ int choose_radix(size_t n1, size_t n2, uint32_t* wbits_out, bool* uneven_out) {
 // One table set per (GPU, circuit, key bytes, radix) in the process: the shards registered on the same HIP device (zkp_hip_init_devices
 // with a device listed twice, as the one-GPU tests do; several contexts of a server) share it instead of holding ~65 GB each.
 struct SharedTables { int hip_dev, kind; uint8_t digest[32]; uint32_t wbits; bool share_ab; uint32_t *g1, *g2; int refs; };      // wbits | uneven << 8; share_ab: laid out with the shared A / B1 slots (g16_share.h)
-struct TableRegistry { std::mutex mu; std::vector<SharedTables> v; std::map<int, std::unique_ptr<std::mutex>> build_mu; };
+struct TableRegistry { std::mutex mu; std::vector<SharedTables> v; std::map<int, std::mutex> build_mu; };
 TableRegistry& table_registry() { static TableRegistry* r = new TableRegistry(); return *r; }
-void release_shared_tables(G16Key& K) {
-    if (K.shared_tables < 0) return;
+std::mutex& table_build_mutex(int hip_dev) { TableRegistry& R = table_registry(); std::lock_guard<std::mutex> lk(R.mu); return R.build_mu[hip_dev]; }
+// Takes a reference to the live entry of `want`'s GPU, circuit, key bytes and share_ab: of exactly its radix, or with any_radix the first
+// one, whose radix K takes with the tables.  false: there is none.
+bool acquire_tables(G16Key& K, const SharedTables& want, bool any_radix) {
     TableRegistry& R = table_registry();
     std::lock_guard<std::mutex> lk(R.mu);
-    SharedTables& e = R.v[(size_t)K.shared_tables];
-    if (--e.refs == 0) { (void)hipFree(e.g1); (void)hipFree(e.g2); e.g1 = e.g2 = nullptr; }
-    K.shared_tables = -1; K.table_g1 = K.table_g2 = nullptr;
+    for (size_t i = 0; i < R.v.size(); i++) {
+        SharedTables& e = R.v[i];
+        if (e.refs <= 0 || e.hip_dev != want.hip_dev || e.kind != want.kind || e.share_ab != want.share_ab || memcmp(e.digest, want.digest, 32) || (!any_radix && e.wbits != want.wbits)) continue;
+        e.refs++; K.shared_tables = (int)i; K.table_g1 = e.g1; K.table_g2 = e.g2; K.rx = g16_radix(e.wbits & 0xffu, (e.wbits >> 8) != 0);
+        return true;
+    }
+    return false;
 }
-
+void register_tables(G16Key& K, SharedTables e) {
+    TableRegistry& R = table_registry();
+    std::lock_guard<std::mutex> lk(R.mu);
+    e.refs = 1; R.v.push_back(e);          // freshly built tables, K their first holder
+    K.shared_tables = (int)R.v.size() - 1; K.table_g1 = e.g1; K.table_g2 = e.g2;
+}
 template <uint32_t AW, class Pt>
 int build_tables(G16Key& K, const std::vector<Pt>& bases, uint32_t** table, bool msm_form, const G16Radix& rx, bool owned = true) {
     std::vector<uint32_t> flat; flat.reserve(bases.size() * AW);
@@ -239,7 +231,12 @@ int build_tables(G16Key& K, const std::vector<Pt>& bases, uint32_t** table, bool
 // everything a key slot holds on the device (a loaded key, or what a failed load got as far as acquiring)
 void release_key(G16Key& K) {
     (void)hipDeviceSynchronize();
-    release_shared_tables(K);
+    if (K.shared_tables >= 0) {          // its reference to the shared MSM tables: the last holder frees them
+        TableRegistry& R = table_registry();
+        std::lock_guard<std::mutex> lk(R.mu);
+        SharedTables& e = R.v[(size_t)K.shared_tables];
+        if (--e.refs == 0) { (void)hipFree(e.g1); (void)hipFree(e.g2); e.g1 = e.g2 = nullptr; }
+    }
     for (void* p : K.allocs) (void)hipFree(p);
     for (auto& e : K.lays_g1) free_layout(e.second.lay);
     for (auto& e : K.lays_g2) free_layout(e.second.lay);
@@ -266,14 +263,13 @@ int load_key_locked(int kind, const uint8_t* pk, uint64_t len) {
 int install_verifying_key(G16Key& K, const G16VkBlob& B) {
     int rc;
     K.vk_ready = false;
-    std::vector<uint32_t> icw; for (auto& e : B.abc) append_words(icw, e.p);
-    append_words(icw, B.alpha_g1.p);                 // point n_ic of the verifier's tables: alpha (the batch check's virtual envelope, g16_rlc.h)
+    std::vector<g1_aff> ic_pts; for (auto& e : B.abc) ic_pts.push_back(e.p);
+    ic_pts.push_back(B.alpha_g1.p);                  // point n_ic of the verifier's tables: alpha (the batch check's virtual envelope, g16_rlc.h)
+    std::vector<uint32_t> icw; for (auto& p : ic_pts) append_words(icw, p);
     const uint32_t* d_ic = nullptr;
     if ((rc = dev_upload(K, &d_ic, icw))) return rc;
     // gamma_abc_g1 are fixed points of the key: the verifier's public-input accumulation walks radix-1024 window tables
     // (the prover's table builder) instead of doubling-and-adding
-    std::vector<g1_aff> ic_pts; for (auto& e : B.abc) ic_pts.push_back(e.p);
-    ic_pts.push_back(B.alpha_g1.p);
     uint32_t* d_ic_tab = nullptr;
     const G16Radix vrx = g16_radix(G16V_WBITS);
     if ((rc = build_tables<20>(K, ic_pts, &d_ic_tab, false, vrx))) return rc;
@@ -297,10 +293,10 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     G16Key& K = g16s().key[kind];
     const HostR1CS cs = kind == G16_EQUALITY ? build_equality_r1cs() : build_membership_r1cs();
     int rc;
-    // ProvingKey { vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query },
+    // parse: ProvingKey { vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query },
     // or its vk alone: a blob that ends behind gamma_abc_g1 is a verifying key (g16_keyblob.h)
     KeyReader R{pk, len};
-    G16VkBlob B;
+    G16VkBlob B; G16PkBlob Q;
     const int format = g16_read_key_prefix(R, B);
     if (format == G16_BLOB_MALFORMED)
         return fail(ZKP_HIP_E_ARGUMENT, "malformed proving key or verifying key (expected ark-serialize uncompressed ProvingKey<Bn254>, or its VerifyingKey<Bn254> alone)");
@@ -308,108 +304,34 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         if (const char* why = g16_check_verifying_key(B, cs.n_inst)) return fail(ZKP_HIP_E_ARGUMENT, why);
         return install_verifying_key(K, B);
     }
-    if ((rc = upload_circuit(K, cs)) || (rc = ensure_mimc_dev())) return rc;
-    const G1Pt &alpha_g1 = B.alpha_g1; const G2Pt &beta_g2 = B.beta_g2, &delta_g2 = B.delta_g2;
-    const std::vector<G1Pt>& abc = B.abc;
-    G1Pt beta_g1, delta_g1;
-    std::vector<G1Pt> aq, b1q, hq, lq; std::vector<G2Pt> b2q;
-    if (parse_g1(R, beta_g1.inf, beta_g1.p) || parse_g1(R, delta_g1.inf, delta_g1.p) ||
-        parse_vec_g1(R, aq) || parse_vec_g1(R, b1q) || parse_vec_g2(R, b2q) || parse_vec_g1(R, hq) || parse_vec_g1(R, lq) || !R.ok || R.left != 0)
-        return fail(ZKP_HIP_E_ARGUMENT, "malformed proving key (expected ark-serialize uncompressed ProvingKey<Bn254>)");
-    if (aq.size() != K.nv || b1q.size() != K.nv || b2q.size() != K.nv || hq.size() != K.m - 1 || lq.size() != K.n_wit || abc.size() != K.n_inst)
-        return fail(ZKP_HIP_E_ARGUMENT, "proving key does not match the circuit shape");
-    if (alpha_g1.inf || beta_g1.inf || delta_g1.inf || beta_g2.inf || delta_g2.inf) return fail(ZKP_HIP_E_ARGUMENT, "degenerate proving key");
-    // scalar rows: z_k (nv) | h_i (m-1) | r | s | -rs | one
-    const uint32_t SC_H = K.nv, SC_R = K.nv + K.m - 1, SC_S = SC_R + 1, SC_NRS = SC_R + 2, SC_ONE = SC_R + 3;
-    // the radix of this key's tables (the point counts are known from the file's vector lengths: a, b1 less the points they share, l, h + delta x3, alpha, beta | b2 + delta, beta)
-    // If another shard of this GPU already holds tables for these key bytes, this shard takes a reference AND their radix (what is free
-    // now -- less than when the first shard chose -- must not pick a smaller one and build a second set); choose_radix only when building.
-    // One load at a time per GPU from here to the registration of freshly built tables.
-    // The slot lists of A and B1, from the key's points alone.  ZKP_HIP_G16_SHARE_AB=0 gives every finite b_g1_query point its own slot
-    // and table again; it is read here, once per load, and tables are shared only between loads that read the same value.
+    if (const char* why = g16_read_proving_key(R, B, g16_key_shape(cs), Q)) return fail(ZKP_HIP_E_ARGUMENT, why);
+    // plan (g16_share.h).  ZKP_HIP_G16_SHARE_AB=0 gives every finite b_g1_query point its own slot and table again; it is read here, once
+    // per load, and tables are shared only between loads that read the same value.
     const bool share_ab = env_int("ZKP_HIP_G16_SHARE_AB", 1) != 0;
-    std::vector<uint8_t> var_class(cs.inst_nwin); var_class.insert(var_class.end(), cs.wit_nwin.begin(), cs.wit_nwin.end());
-    const G16AbSlots ab = g16_ab_slots(aq, b1q, var_class, share_ab);
-    uint8_t digest[32]; sha256_host(digest, pk, len);
-    TableRegistry& TR = table_registry();
-    std::mutex* bm = nullptr;
-    { std::lock_guard<std::mutex> lk(TR.mu); auto& up = TR.build_mu[dev().hip_dev]; if (!up) up.reset(new std::mutex()); bm = up.get(); }
-    std::lock_guard<std::mutex> build_lock(*bm);
-    {
-        const bool forced = env_int("ZKP_HIP_G16_WBITS", 0) != 0;
-        uint32_t wb = 0; bool uneven = false; int found = -1;
-        {
-            std::lock_guard<std::mutex> lk(TR.mu);
-            for (size_t i = 0; i < TR.v.size() && !forced; i++)
-                if (TR.v[i].refs > 0 && TR.v[i].hip_dev == dev().hip_dev && TR.v[i].kind == kind && TR.v[i].share_ab == share_ab && !memcmp(TR.v[i].digest, digest, 32)) {
-                    found = (int)i; TR.v[i].refs++; wb = TR.v[i].wbits & 0xffu; uneven = (TR.v[i].wbits >> 8) != 0;
-                    K.shared_tables = found; K.table_g1 = TR.v[i].g1; K.table_g2 = TR.v[i].g2;
-                    break;
-                }
+    G16KeyPlan P;
+    if (const char* why = g16_plan_key(P, B, Q, cs, share_ab)) return fail(ZKP_HIP_E_UNSUPPORTED, why);
+    // the radix.  If another shard of this GPU already holds tables for these key bytes, this shard takes a reference AND their radix (what
+    // is free now -- less than when the first shard chose -- must not pick a smaller one and build a second set); choose_radix only when
+    // building.  A forced radix (ZKP_HIP_G16_WBITS) shares only an entry of exactly that radix.  One load at a time per GPU from here on.
+    SharedTables want{}; want.hip_dev = dev().hip_dev; want.kind = kind; want.share_ab = share_ab; sha256_host(want.digest, pk, len);
+    std::lock_guard<std::mutex> build_lock(table_build_mutex(want.hip_dev));
+    if (env_int("ZKP_HIP_G16_WBITS", 0) != 0 || !acquire_tables(K, want, true)) {
+        uint32_t wb = 0; bool uneven = false;
+        if ((rc = choose_radix(P.radix_points_g1, P.radix_points_g2, &wb, &uneven))) return rc;
+        K.rx = g16_radix(wb, uneven); want.wbits = K.rx.wbits | K.rx.uneven << 8;
+        if (!acquire_tables(K, want, false)) {       // the MSM tables: built here
+            if ((rc = build_tables<20>(K, P.bases_g1, &want.g1, true, K.rx, false))) return rc;
+            if ((rc = build_tables<40>(K, P.bases_g2, &want.g2, true, K.rx, false))) { (void)hipFree(want.g1); return rc; }
+            register_tables(K, want);
         }
-        if (found < 0 && (rc = choose_radix(aq.size() + b1q.size() - ab.s.size() + lq.size() + hq.size() + 5, b2q.size() + 2, &wb, &uneven))) return rc;
-        K.rx = g16_radix(wb, uneven);
     }
-    const uint32_t NWIN = K.rx.nwin;
-    auto var_nwin = [&](uint32_t k) -> uint8_t { return g16_class_nwin(k < cs.n_inst ? cs.inst_nwin[k] : cs.wit_nwin[k - cs.n_inst], K.rx); };
-    std::vector<g1_aff> bases1; std::vector<g2_aff> bases2;
-    std::vector<uint16_t> scal1, scal2;
-    std::vector<SlotList> t1(4), t2(1);               // G1: A' | S | B1' | C
-    auto add1 = [&](int target, const G1Pt& pt, uint32_t scal, uint8_t nwin) {
-        if (pt.inf) return;
-        t1[target].push_back({(uint16_t)bases1.size(), nwin}); bases1.push_back(pt.p); scal1.push_back((uint16_t)scal);
-    };
-    auto add2 = [&](const G2Pt& pt, uint32_t scal, uint8_t nwin) {
-        if (pt.inf) return;
-        t2[0].push_back({(uint16_t)bases2.size(), nwin}); bases2.push_back(pt.p); scal2.push_back((uint16_t)scal);
-    };
-    if (K.nv + K.m + 3 > 65535 || 3ull * K.nv + K.m + 8 > 65535) return fail(ZKP_HIP_E_UNSUPPORTED, "circuit too large for 16-bit slot indices");
-    // A = alpha + sum z_k a_k + r delta ; B = beta + sum z_k b_k + s delta ; Cp = sum aux_k l_k + sum h_i H_i - rs delta
-    // (a variable whose a_query and b_g1_query points are one point has its slot in S, once, and no b_g1_query table: g16_share.h)
-    for (auto& sl : ab.a) add1(0, aq[sl.first], sl.first, var_nwin(sl.first));
-    add1(0, delta_g1, SC_R, NWIN); add1(0, alpha_g1, SC_ONE, 1);
-    for (auto& sl : ab.s) add1(1, aq[sl.first], sl.first, var_nwin(sl.first));
-    for (auto& sl : ab.b) add1(2, b1q[sl.first], sl.first, var_nwin(sl.first));
-    add1(2, delta_g1, SC_S, NWIN); add1(2, beta_g1, SC_ONE, 1);
-    for (uint32_t k = 0; k < K.n_wit; k++) add1(3, lq[k], K.n_inst + k, var_nwin(K.n_inst + k));
-    for (uint32_t i = 0; i + 1 < K.m; i++) add1(3, hq[i], SC_H + i, NWIN);
-    add1(3, delta_g1, SC_NRS, NWIN);
-    for (uint32_t k = 0; k < K.nv; k++) add2(b2q[k], k, var_nwin(k));
-    add2(delta_g2, SC_S, NWIN); add2(beta_g2, SC_ONE, 1);
-    // make_layout keeps insertion order, so slot s of the layout <-> entry s of bases/scal when targets are laid out in order
-    {
-        std::vector<g1_aff> ob; std::vector<uint16_t> os;
-        for (auto& t : t1) for (auto& sl : t) { ob.push_back(bases1[sl.first]); os.push_back(scal1[sl.first]); }
-        uint16_t idx = 0; for (auto& t : t1) for (auto& sl : t) sl.first = idx++;
-        bases1.swap(ob); scal1.swap(os);
-    }
-    K.targets_g1 = t1; K.targets_g2 = t2;
-    for (auto& t : t1) for (auto& sl : t) K.win_g1 += sl.second;
-    for (auto& t : t2) for (auto& sl : t) K.win_g2 += sl.second;
-    K.hscal_g1 = scal1; K.hscal_g2 = scal2;
+    K.table_bytes = key_table_bytes(P.bases_g1.size(), P.bases_g2.size(), K.rx.wbits, K.rx.uneven);
+    if ((rc = upload_circuit(K, cs)) || (rc = ensure_mimc_dev())) return rc;
+    K.targets_g1 = g16_plan_targets(P.cls_g1, K.rx); K.targets_g2 = g16_plan_targets(P.cls_g2, K.rx);
+    K.win_g1 = g16_windows(K.targets_g1); K.win_g2 = g16_windows(K.targets_g2);
+    K.hscal_g1 = P.row_g1; K.hscal_g2 = P.row_g2;
     if ((rc = upload_offset_point(K, false, &K.init_g1)) || (rc = upload_offset_point(K, true, &K.init_g2))) return rc;
-    if (K.shared_tables < 0) {   // the MSM tables: built here unless the registry had them (above)
-        TableRegistry& R = TR;
-        int found = -1;
-        {
-            std::lock_guard<std::mutex> lk(R.mu);         // (a forced radix skipped the adoption above: an entry of exactly that radix is still shared)
-            for (size_t i = 0; i < R.v.size(); i++)
-                if (R.v[i].refs > 0 && R.v[i].hip_dev == dev().hip_dev && R.v[i].kind == kind && R.v[i].wbits == (K.rx.wbits | K.rx.uneven << 8) && R.v[i].share_ab == share_ab && !memcmp(R.v[i].digest, digest, 32)) { found = (int)i; R.v[i].refs++; break; }
-        }
-        if (found < 0) {
-            uint32_t *t1 = nullptr, *t2 = nullptr;
-            if ((rc = build_tables<20>(K, bases1, &t1, true, K.rx, false))) return rc;
-            if ((rc = build_tables<40>(K, bases2, &t2, true, K.rx, false))) { (void)hipFree(t1); return rc; }
-            std::lock_guard<std::mutex> lk(R.mu);
-            SharedTables e{}; e.hip_dev = dev().hip_dev; e.kind = kind; memcpy(e.digest, digest, 32); e.wbits = K.rx.wbits | K.rx.uneven << 8; e.share_ab = share_ab; e.g1 = t1; e.g2 = t2; e.refs = 1;
-            R.v.push_back(e); found = (int)R.v.size() - 1;
-        }
-        std::lock_guard<std::mutex> lk(R.mu);
-        K.shared_tables = found; K.table_g1 = R.v[(size_t)found].g1; K.table_g2 = R.v[(size_t)found].g2;
-    }
-    K.table_bytes = key_table_bytes(bases1.size(), bases2.size(), K.rx.wbits, K.rx.uneven);
     // the verifying key that leads the file; one that cannot verify (gamma or a gamma_abc_g1 point at infinity) leaves a key that only proves
-    K.vk_ready = false;
     if (!g16_check_verifying_key(B, K.n_inst) && (rc = install_verifying_key(K, B))) return rc;
     K.loaded = true;
     return 0;
@@ -422,13 +344,19 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
 // (ark-groth16 draws random generators; any generator pair yields a valid key).
 fr tape_fr(const uint32_t seed[8], uint32_t idx, uint32_t slot) { uint32_t w[16]; tape_draw64(w, seed, idx, slot); return fp_from_wide<FrParams>(w); }
 
+// the view k_msm_gather gets of one launch over a key's tables: the radix's table shape, an uploaded layout, the digit row of its slots
+MsmView g16_msm_view(const G16Radix& rx, const DevLayout& D, const uint16_t* slot_scalar, const uint32_t* table, const uint32_t* acc_init, uint32_t rows, const uint32_t* digits, uint32_t* partial) {
+    MsmView m; m.nwin = rx.nwin; m.nent = rx.nent; m.digw = rx.digw; m.slot_ent = rx.slot_ent; m.uneven = rx.uneven; m.rows = rows; m.nslots = D.nslots; m.nchunks = D.nchunks; m.table = table; m.digits = digits;
+    m.slot_base = D.slot_base; m.slot_scalar = slot_scalar; m.slot_nwin = D.slot_nwin; m.chunk_begin = D.chunk_begin; m.chunk_win0 = D.chunk_win0; m.chunk_nwin = D.chunk_nwin; m.partial = partial; m.acc_init = acc_init;
+    m.steps = D.steps; m.chunk_step0 = D.chunk_step0;
+    return m;
+}
+
 int gpu_scalar_mults(bool g2, const std::vector<fr>& scalars, std::vector<uint8_t>& out_bytes) {
     const uint32_t rows = (uint32_t)scalars.size(), AW = g2 ? 40 : 20, JW = g2 ? G2_JAC_W : G1_JAC_W, PB = g2 ? 128 : 64;
     std::vector<uint32_t> base;
     if (!g2) append_words(base, host_g1_generator()); else append_words(base, host_g2_generator());
-    ensure_offsets();
-    std::vector<uint32_t> offs;      // [O | -O]
-    if (!g2) { append_words(offs, g_off.o1); append_words(offs, jac_neg(g_off.o1)); } else { append_words(offs, g_off.o2); append_words(offs, jac_neg(g_off.o2)); }
+    std::vector<uint32_t> offs; append_offset(offs, g2, 0); append_offset(offs, g2, 1);      // [O | -O]
     const G16Radix rx = g16_radix(10);           // one base point, thousands of scalars: a small table is plenty
     std::vector<uint32_t> dig((size_t)rx.digw * rows);
     for (uint32_t i = 0; i < rows; i++) {
@@ -436,33 +364,19 @@ int gpu_scalar_mults(bool g2, const std::vector<fr>& scalars, std::vector<uint8_
         for (uint32_t k = 0; k < rx.digw; k++) dig[(size_t)k * rows + i] = pk[k];
     }
     uint32_t *d_base = nullptr, *d_tab = nullptr, *d_dig = nullptr, *d_part = nullptr, *d_offs = nullptr, *d_sums = nullptr; uint8_t* d_out = nullptr;
-    uint16_t* d_meta = nullptr; uint8_t* d_nwin = nullptr; uint32_t* d_steps = nullptr;
     DevScope mem;
     HIP_TRY(mem.alloc(&d_base, AW * 4)); HIP_TRY(mem.alloc(&d_tab, (size_t)rx.slot_ent * g16_table_entry_words(g2, true) * 4 + 64)); HIP_TRY(mem.alloc(&d_dig, dig.size() * 4));
     HIP_TRY(mem.alloc(&d_part, (size_t)JW * 4 * rows)); HIP_TRY(mem.alloc(&d_sums, (size_t)JW * 4 * rows)); HIP_TRY(mem.alloc(&d_offs, offs.size() * 4));
-    HIP_TRY(hipMemcpy(d_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice)); HIP_TRY(mem.alloc(&d_out, (size_t)PB * rows)); HIP_TRY(mem.alloc(&d_meta, 32)); HIP_TRY(mem.alloc(&d_nwin, 16));
-    const uint16_t meta[7] = {0, 0, 0, 0, (uint16_t)rx.nwin, 0, 1};  // slot_base, slot_scalar, chunk_begin, chunk_win0, chunk_nwin of the single chunk; target_chunk_begin = {0, 1}
-    const uint8_t nwin = (uint8_t)rx.nwin;
+    HIP_TRY(hipMemcpy(d_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice)); HIP_TRY(mem.alloc(&d_out, (size_t)PB * rows));
     HIP_TRY(hipMemcpy(d_base, base.data(), AW * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_dig, dig.data(), dig.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_meta, meta, 14, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_nwin, &nwin, 1, hipMemcpyHostToDevice));
-    uint32_t steps_words = 0;
-    {   // the one chunk's step list: slot 0, every window of the radix
-        MsmLayout L1; L1.slot_base = {0}; L1.slot_nwin = {(uint8_t)rx.nwin}; L1.chunk_begin = {0}; L1.chunk_win0 = {0}; L1.chunk_nwin = {(uint16_t)rx.nwin}; L1.target_chunk_begin = {0, 1};
-        std::vector<uint32_t> steps, step0;
-        const GatherShape shape{rx.nent, rx.slot_ent, rx.uneven ? 1u : 0u, rx.digw};
-        if (!make_gather_steps(L1, nullptr, shape, steps, step0)) return fail(ZKP_HIP_E_UNSUPPORTED, "window tables of more than 2^32 entries");
-        steps.insert(steps.end(), step0.begin(), step0.end());            // [steps | chunk_step0]
-        HIP_TRY(mem.alloc(&d_steps, steps.size() * 4));
-        HIP_TRY(hipMemcpy(d_steps, steps.data(), steps.size() * 4, hipMemcpyHostToDevice));
-        steps_words = (uint32_t)(steps.size() - step0.size());
-    }
+    // one slot (base 0, digit row 0, every window of the radix) in one chunk of one target
+    struct OneSlot { DevLayout d; ~OneSlot() { free_layout(d); } } lay;
+    const GatherShape shape{rx.nent, rx.slot_ent, rx.uneven ? 1u : 0u, rx.digw};
+    if (int rc = upload_layout(lay.d, make_layout_even({SlotList{{0, (uint8_t)rx.nwin}}}, 1), &shape)) return rc;
     g16_launch_build_table(g2, d_base, 1, d_tab, dev().stream, true, rx);
-    MsmView m; m.nwin = rx.nwin; m.nent = rx.nent; m.digw = rx.digw; m.slot_ent = rx.slot_ent; m.uneven = rx.uneven; m.rows = rows; m.nslots = 1; m.nchunks = 1; m.table = d_tab; m.digits = d_dig;
-    m.slot_base = d_meta; m.slot_scalar = d_meta + 1; m.slot_nwin = d_nwin; m.chunk_begin = d_meta + 2; m.chunk_win0 = d_meta + 3; m.chunk_nwin = d_meta + 4; m.partial = d_part; m.acc_init = d_offs;
-    m.steps = d_steps; m.chunk_step0 = d_steps + steps_words;
-    g16_launch_msm(g2, m, dev().stream);
-    ReduceView R{}; R.rows = rows; R.ntargets = 1; R.partial = d_part; R.target_chunk_begin = d_meta + 5; R.corr = d_offs + JW;
+    g16_launch_msm(g2, g16_msm_view(rx, lay.d, nullptr, d_tab, d_offs, rows, d_dig, d_part), dev().stream);
+    ReduceView R{}; R.rows = rows; R.ntargets = 1; R.partial = d_part; R.target_chunk_begin = lay.d.target_chunk_begin; R.corr = d_offs + JW;
     g16_launch_sum(g2, R, d_sums, dev().stream);
     g16_launch_serialize(g2, d_sums, rows, d_out, dev().stream);
     out_bytes.resize((size_t)PB * rows);
@@ -530,10 +444,8 @@ int generate_key_locked(int kind, const uint8_t* setup_seed, std::vector<uint8_t
 }
 
 int launch_msm_key(bool g2, const G16Radix& rx, const G16Key::Chunking& ch, const uint32_t* table, const uint32_t* acc_init, uint32_t rows, const uint32_t* digits, uint32_t* partial, hipStream_t st) {
-    const DevLayout& D = ch.lay; const uint16_t* slot_scalar = ch.scal;
-    MsmView m; m.nwin = rx.nwin; m.nent = rx.nent; m.digw = rx.digw; m.slot_ent = rx.slot_ent; m.uneven = rx.uneven; m.rows = rows; m.nslots = D.nslots; m.nchunks = D.nchunks; m.table = table; m.digits = digits;
-    m.slot_base = D.slot_base; m.slot_scalar = slot_scalar; m.slot_nwin = D.slot_nwin; m.chunk_begin = D.chunk_begin; m.chunk_win0 = D.chunk_win0; m.chunk_nwin = D.chunk_nwin; m.partial = partial; m.acc_init = acc_init;
-    m.steps = D.steps; m.chunk_step0 = D.chunk_step0;
+    const DevLayout& D = ch.lay;
+    const MsmView m = g16_msm_view(rx, D, ch.scal, table, acc_init, rows, digits, partial);
     Device::KProf& K = dev().prof[g2 ? 2 : 1];
     hipEvent_t e1 = nullptr;
     int rc = prof_begin(K, st, &e1);
@@ -684,12 +596,7 @@ void g16_release_all() {
         if (W.last) { for (auto e : W.ev) (void)hipEventDestroy(e); (void)hipEventDestroy(W.last); }
         if (W.buf) (void)hipFree(W.buf);
     }
-    for (auto& K : S->key) {
-        release_shared_tables(K);
-        for (void* p : K.allocs) (void)hipFree(p);
-        for (auto& e : K.lays_g1) free_layout(e.second.lay);
-        for (auto& e : K.lays_g2) free_layout(e.second.lay);
-    }
+    for (auto& K : S->key) release_key(K);
     if (S->mimc_dev) (void)hipFree(S->mimc_dev);
     g16_vm_free(S->vm);
     delete S; dev().g16 = nullptr;

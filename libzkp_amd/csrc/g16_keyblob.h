@@ -78,4 +78,21 @@ inline const char* g16_check_verifying_key(const G16VkBlob& vk, uint32_t n_inst)
     return nullptr;
 }
 
+// What follows the verifying key in ProvingKey<Bn254>: beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query
+struct G16PkBlob { G1Pt beta_g1{}, delta_g1{}; std::vector<G1Pt> a_query, b_g1_query, h_query, l_query; std::vector<G2Pt> b_g2_query; };
+// the vector lengths of a circuit's key: nv variables (n_inst instance ones, the constant one included, and n_wit witnesses), domain size m
+struct G16KeyShape { uint32_t nv, m, n_wit, n_inst; };
+// Reads the rest of a proving key (R as g16_read_key_prefix left it) and checks it against the circuit: nullptr, or the message of the first
+// rule it breaks -- the format (nothing may follow l_query), the vector lengths, a key point no proof can do without at infinity
+inline const char* g16_read_proving_key(KeyReader& R, const G16VkBlob& vk, const G16KeyShape& s, G16PkBlob& pk) {
+    if (parse_g1(R, pk.beta_g1.inf, pk.beta_g1.p) || parse_g1(R, pk.delta_g1.inf, pk.delta_g1.p) || parse_vec_g1(R, pk.a_query) || parse_vec_g1(R, pk.b_g1_query) ||
+        parse_vec_g2(R, pk.b_g2_query) || parse_vec_g1(R, pk.h_query) || parse_vec_g1(R, pk.l_query) || !R.ok || R.left != 0)
+        return "malformed proving key (expected ark-serialize uncompressed ProvingKey<Bn254>)";
+    if (pk.a_query.size() != s.nv || pk.b_g1_query.size() != s.nv || pk.b_g2_query.size() != s.nv || pk.h_query.size() != s.m - 1 || pk.l_query.size() != s.n_wit ||
+        vk.abc.size() != s.n_inst)
+        return "proving key does not match the circuit shape";
+    if (vk.alpha_g1.inf || pk.beta_g1.inf || pk.delta_g1.inf || vk.beta_g2.inf || vk.delta_g2.inf) return "degenerate proving key";
+    return nullptr;
+}
+
 }  // namespace zkp

@@ -1,7 +1,9 @@
 """The key points that the Groth16 sums A and B1 share (libzkp_amd/csrc/g16_share.h), on the CPU: the committed keys' 110 shared
 variables, the windows the A / B1 launch loses, the three slot lists A' | S | B1' read back from the step lists of several chunkings
 (every (point, scalar row, window) of A and of B1 exactly once), the degenerate keys, and one launch walked on the host against
-double-and-add.  tests/emul/emul_g16_shared_points.cpp is a program of its own: it is run once as built, and once built with the host
+double-and-add.  The slots come from the key loader's own plan (g16_share.h), whose other decisions are checked here too: lists C and
+G2, scalar rows, windows, base order, the point counts the radix is chosen from, the offset corrections of every sum, and the
+proving-key reader's rules (g16_keyblob.h).  tests/emul/emul_g16_shared_points.cpp is a program of its own: it is run once as built, and once built with the host
 sanitizers."""
 import os
 import subprocess
@@ -11,10 +13,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "emul", "emul_g16_shared_points.cpp")
 KEYS = [os.path.join(ROOT, "tests", "golden", name) for name in ("equality_mimc_pk.bin", "membership_mimc_pk.bin")]
-CHECKS = (["shared_count_%s" % c for c in ("equality", "membership")]
-          + ["%s_%s_w%d" % (what, c, w) for what in ("windows_fall", "switch_off_is_parent", "each_term_once") for c in ("equality", "membership") for w in (13, 8)]
+CIRCUITS = ("equality", "membership")
+CHECKS = (["shared_count_%s" % c for c in CIRCUITS]
+          + ["%s_%s_w%d" % (what, c, w) for what in ("windows_fall", "switch_off_is_parent", "each_term_once") for c in CIRCUITS for w in (13, 8)]
           + ["no_coincidence_is_parent_layout", "infinity_pair_ignored", "different_index_ignored", "negation_not_shared",
-             "msm_walk_w8", "msm_walk_w13", "msm_walk_w14_uneven"])
+             "msm_walk_w8", "msm_walk_w13", "msm_walk_w14_uneven"]
+          # the loader's whole plan (g16_share.h): lists C and G2, scalar rows and windows, base order, window sums, with the switch on and off
+          + ["%s_%s_w%d" % (what, c, w) for what in ("lists_c_g2", "rows_windows", "slot_is_base", "window_sums") for c in CIRCUITS for w in (13, 8)]
+          + ["point_counts_%s_%s" % (c, sw) for c in CIRCUITS for sw in ("shared", "switch_off")] + ["table_points_%s" % c for c in CIRCUITS]
+          + ["offset_counts_%s" % c for c in CIRCUITS + ("synthetic",)]
+          + ["reader_accepts_committed_key", "reader_truncated", "reader_trailing_bytes", "reader_a_query_length", "reader_delta_g1_infinity"])
 
 
 def build_and_run(tmp, name, flags):
