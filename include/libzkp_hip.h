@@ -61,7 +61,9 @@ int zkp_hip_init(int device);
 int zkp_hip_init_devices(uint32_t count, const int* devices);
 int zkp_hip_device_count(void);                      /* shards registered */
 /* The per-variant entry points (everything except the batch calls below) run on ONE shard: shard 0 unless the calling
- * thread selected another one here (thread-local; concurrent callers on different shards do not serialise). */
+ * thread selected another one here (thread-local; concurrent callers on different shards do not serialise).  The exception: the six
+ * zkp_hip_verify_*_batch calls of a thread that has NEVER called this spread a large call over every registered shard ("Verification over
+ * every registered GPU" below); a thread that has selected a shard -- shard 0 included -- does its own splitting and stays on it. */
 int zkp_hip_use_device(int shard);
 /* Releases every device resource of every shard (tables, loaded keys, workspaces, pooled staging buffers, streams, pinned
  * staging) and forgets the shard registration; a later call initialises again (keys must be loaded again; batches staged
@@ -155,6 +157,21 @@ int zkp_hip_snark_commit_value_batch(uint64_t n, const uint64_t* values, uint8_t
 int zkp_hip_prove_equality_batch(uint64_t n, const uint64_t* val1, const uint64_t* val2, const uint8_t* seeds,
                                  uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status);
 
+/* ---- Verification over every registered GPU.  With more than one shard registered (zkp_hip_init_devices), each of the six
+ * zkp_hip_verify_*_batch calls below cuts its n envelopes into contiguous slices, in order, one per participating shard, and runs every slice
+ * through the same verifier on that shard (the shards' host workers, as the batch calls do); verdicts land in ok[] where they always did.
+ * Slices are balanced by weight in the verifiers' jobs (range envelope 2; threshold, equality, membership, improvement 1; consistency its
+ * k - 1, at least 1) and there are min(shards, total weight / minimum) of them -- fewer when a slice would weigh less than the minimum --
+ * so a call below twice the minimum stays on one shard.  The minimum is the scheme's batch-check threshold in force (ZKP_HIP_BATCH_VERIFY_MIN,
+ * default 4096 jobs; ZKP_HIP_G16_BATCH_VERIFY_MIN, default 8193 envelopes): every slice takes the one-check path a whole call of its size
+ * takes.  Improvement proofs have no batch check: their minimum is what fills one GPU with k_stark_verify workgroups (64 envelopes each).
+ * SOUNDNESS IS PER SLICE: every slice draws its own fresh weights and makes its own batch check, with its own fallback and localisation; the
+ * error bounds stated below hold per slice, and nothing is combined across GPUs.  Verdicts are those of the call on one shard.
+ * Participants: the shards in registration order from the caller's; for Groth16 only shards that hold a usable key of the circuit (if the
+ * caller's shard holds none the call fails as on one shard).  The call stays on the caller's shard when one shard is registered, when
+ * ZKP_HIP_VERIFY_SHARDS=0, or when the calling thread has selected a shard with zkp_hip_use_device.  ZKP_HIP_VERIFY_SHARD_MIN=<jobs>
+ * replaces the minimum for every scheme.  Both switches are read on every call.  A negative code from any slice fails the call with that
+ * slice's message.  Counted: zkp_hip_profile_read_kernel(ZKP_HIP_COUNTER_VERIFY_FANOUT, ...). */
 /* Replaces a loop of proof::range_proof::verify_range(proof, min, max) (range_proof.rs:28-47 ->
  * BulletproofsBackend::verify_range_with_bounds, bulletproofs.rs:181-295).  proofs = n envelopes at `stride` bytes,
  * lens[i] bytes used.  ok[i] = 1 accepted, 0 rejected (malformed framing, wrong bounds, invalid points/scalars, failed
@@ -309,7 +326,11 @@ enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_
        /* Not a kernel: the self-check of flagged batches (ZKP_HIP_OP_SELF_CHECK).  Always counted, summed over the shards, same `reset`.
         * *launches = ops whose envelope went through its verifier; *point_adds = ops refused by the self-check; *ms = host wall time from the end
         * of proving to the end of verification (verdicts applied, proofs packed). */
-       ZKP_HIP_COUNTER_BATCH_SELF_CHECK = 4 };
+       ZKP_HIP_COUNTER_BATCH_SELF_CHECK = 4,
+       /* Not a kernel: zkp_hip_verify_*_batch calls that were spread over several shards (see "Verification over every registered GPU" above).
+        * Always counted, per shard, summed over the shards, same `reset`.  *launches = slices run by fanned-out calls; *point_adds = envelopes in
+        * those slices; *ms = host wall time of the fanned-out calls, measured in the calling thread.  A call that stayed on one shard counts nothing. */
+       ZKP_HIP_COUNTER_VERIFY_FANOUT = 5 };
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset);
 int zkp_hip_profile_read(double* msm_ms, uint64_t* msm_launches, uint64_t* msm_point_adds, int reset);
 /* Tunable (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned

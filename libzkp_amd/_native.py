@@ -13,6 +13,7 @@ RANGE_PROOF_BYTES = 1478
 TABLES_BP_GENERATORS = 2          # zkp_hip_groth16_key_info kind: the Bulletproofs generator tables (include/libzkp_hip.h)
 COUNTER_G16_VERIFY = 3            # zkp_hip_profile_read_kernel id: what the Groth16 verifier did after failed batch checks (include/libzkp_hip.h)
 COUNTER_BATCH_SELF_CHECK = 4      # zkp_hip_profile_read_kernel id: ops verified / refused by the self-check of flagged batches (include/libzkp_hip.h)
+COUNTER_VERIFY_FANOUT = 5         # zkp_hip_profile_read_kernel id: slices / envelopes / host ms of verify calls spread over several shards (include/libzkp_hip.h)
 OP_SELF_CHECK = 0x100             # ZKP_HIP_OP_SELF_CHECK: OR-ed into the kind of every op of a batch that verifies its own proofs before release
 # symbols declared in include/libzkp_hip.h (checked by tests/test_abi.py)
 EXPORTS = (

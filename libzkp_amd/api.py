@@ -552,6 +552,18 @@ def batch_self_check_counters(reset=True):
     return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
 
 
+def verify_fanout_counters(reset=True):
+    """What the verify_*_batch calls that were spread over several registered shards did, summed over the shards since the last reset
+    (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_VERIFY_FANOUT; always counted): {"launches": slices run by fanned-out calls,
+    "point_adds": envelopes in those slices, "ms": host wall time of the fanned-out calls}.  A call that stayed on one shard -- one shard
+    registered, ZKP_HIP_VERIFY_SHARDS=0, a thread that selected a shard, less than two minimum slices of work -- counts nothing.
+    reset=True zeroes the counters."""
+    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_VERIFY_FANOUT, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
+                  "zkp_hip_profile_read_kernel")
+    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+
+
 def verify_equality_with_commitment_batch(proofs, commitments):
     """Batched verify_equality_with_commitment (equality_proof.rs:34-60): the envelope must carry exactly that commitment."""
     blobs = [bytes(p) for p in proofs]

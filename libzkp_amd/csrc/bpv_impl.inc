@@ -133,18 +133,21 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
     return 0;
 }
 
+// jobs of each consistency envelope, read from its own k field (k - 1 range proofs; 0 for an envelope the device step will reject)
+std::vector<uint32_t> consistency_job_counts(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens) {
+    std::vector<uint32_t> job_counts(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t* env = proofs + stride * i; uint64_t k = 0;
+        if (lens[i] <= stride && lens[i] >= 14) k = (uint64_t)env[10] | ((uint64_t)env[11] << 8) | ((uint64_t)env[12] << 16) | ((uint64_t)env[13] << 24);
+        const bool fits = k >= 1 && k < (1u << 20) && 10 + 4 + 32 * k + (uint64_t)(4 + RP_BYTES + 32) * (k - 1) + 32 <= lens[i];
+        job_counts[i] = fits ? (uint32_t)(k - 1) : 0u;       // the device step rejects an envelope whose k disagrees
+    }
+    return job_counts;
+}
 // the host-buffer entry points: upload, then the core above (the consistency job counts are read from the envelopes' own k fields)
 int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
     std::vector<uint32_t> job_counts;
-    if (scheme == 6) {
-        job_counts.resize(n);
-        for (uint64_t i = 0; i < n; i++) {
-            const uint8_t* env = proofs + stride * i; uint64_t k = 0;
-            if (lens[i] <= stride && lens[i] >= 14) k = (uint64_t)env[10] | ((uint64_t)env[11] << 8) | ((uint64_t)env[12] << 16) | ((uint64_t)env[13] << 24);
-            const bool fits = k >= 1 && k < (1u << 20) && 10 + 4 + 32 * k + (uint64_t)(4 + RP_BYTES + 32) * (k - 1) + 32 <= lens[i];
-            job_counts[i] = fits ? (uint32_t)(k - 1) : 0u;       // the device step rejects an envelope whose k disagrees
-        }
-    }
+    if (scheme == 6) job_counts = consistency_job_counts(n, proofs, stride, lens);
     hipStream_t st = dev().stream;
     uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t *d_min = nullptr, *d_max = nullptr;
     DevScope mem;
@@ -156,6 +159,20 @@ int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t str
     if (mins) HIP_TRY(hipMemcpyAsync(d_min, mins, 8 * n, hipMemcpyHostToDevice, st));
     if (maxs) HIP_TRY(hipMemcpyAsync(d_max, maxs, 8 * n, hipMemcpyHostToDevice, st));
     return verify_bp_device(scheme, n, d_in, stride, d_len, d_min, d_max, d_ok, job_counts.data(), ok);
+}
+
+// The same over every registered shard when the plan of verify_shards.h says so (*fanned), one slice per shard through verify_bp_locked: every
+// slice draws its own weights and makes its own batch check.  Minimum slice: the batch-check threshold in force (ZKP_HIP_BATCH_VERIFY_MIN).
+int verify_bp_fanned(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok, bool* fanned) {
+    *fanned = false;
+    const std::vector<Device*> shards = verify_fanout_candidates();
+    if (shards.empty()) return 0;
+    std::vector<uint64_t> prefix;
+    if (scheme == 6) { prefix.resize(n + 1); vs_prefix(n, consistency_job_counts(n, proofs, stride, lens).data(), prefix.data()); }
+    const int rlc_min = env_int("ZKP_HIP_BATCH_VERIFY_MIN", (int)RLC_MIN_JOBS);
+    return verify_fan_out(shards, nullptr, n, scheme == 6 ? prefix.data() : nullptr, scheme == 1 ? 2u : 1u, rlc_min > 0 ? (uint64_t)rlc_min : RLC_MIN_JOBS,
+                          [&](uint64_t lo, uint64_t m) { return verify_bp_locked(scheme, m, proofs + stride * lo, stride, lens + lo, mins ? mins + lo : nullptr, maxs ? maxs + lo : nullptr, ok + lo); },
+                          fanned);
 }
 
 void bpv_release_all() {
@@ -171,22 +188,37 @@ extern "C" {
 
 int zkp_hip_verify_range_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) try {
     if (n == 0) return 0;
-    Bind bind; int rc = verifier_args(n, {proofs, lens, mins, maxs, ok}, stride);
-    if (rc || (rc = bind.open())) return rc;
+    int rc = verifier_args(n, {proofs, lens, mins, maxs, ok}, stride);
+    if (rc) return rc;
+    bool fanned = false;
+    rc = verify_bp_fanned(1, n, proofs, stride, lens, mins, maxs, ok, &fanned);
+    if (rc || fanned) return rc;
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return verify_bp_locked(1, n, proofs, stride, lens, mins, maxs, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_threshold_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* thresholds, uint8_t* ok) try {
     if (n == 0) return 0;
-    Bind bind; int rc = verifier_args(n, {proofs, lens, thresholds, ok}, stride);
-    if (rc || (rc = bind.open())) return rc;
+    int rc = verifier_args(n, {proofs, lens, thresholds, ok}, stride);
+    if (rc) return rc;
+    bool fanned = false;
+    rc = verify_bp_fanned(3, n, proofs, stride, lens, thresholds, nullptr, ok, &fanned);
+    if (rc || fanned) return rc;
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return verify_bp_locked(3, n, proofs, stride, lens, thresholds, nullptr, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_consistency_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc || (rc = bind.open())) return rc;
+    int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc) return rc;
+    bool fanned = false;
+    rc = verify_bp_fanned(6, n, proofs, stride, lens, nullptr, nullptr, ok, &fanned);
+    if (rc || fanned) return rc;
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return verify_bp_locked(6, n, proofs, stride, lens, nullptr, nullptr, ok);
 } ZKP_API_CATCH_INT
 

@@ -682,6 +682,9 @@ int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, cons
     return 0;
 }
 
+// ZKP_HIP_G16_BATCH_VERIFY_MIN: measured crossover, a single round of the per-envelope chains (<= 8192 envelopes) is faster than the batch check (profiles/r04_verify_g16_batch.json)
+int g16_rlc_min() { static const int v = env_int("ZKP_HIP_G16_BATCH_VERIFY_MIN", 8193); return v; }
+
 // Verdicts of n envelopes that lie in device memory (d_in, `stride` bytes each, d_len[i] bytes used) into d_ok (device) and ok (host, n bytes:
 // the localisation pass reads the batch check's verdicts there): one weighted pairing check for a large batch (g16_rlc.h); when it does not
 // stand, the localisation pass and the per-envelope check of the suspect envelopes, or of all of them.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test
@@ -705,7 +708,7 @@ int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, 
         // multiplications per envelope, the loops on gamma / delta and the final exponentiation once.  Its verdicts stand when the batch's
         // product is one and no envelope needs the per-envelope treatment; otherwise (a tampered envelope, a point at infinity) the suspect
         // envelopes, or all of them, are verified again envelope by envelope below, so the answer is always the per-envelope one.
-        static const int rlc_min = env_int("ZKP_HIP_G16_BATCH_VERIFY_MIN", 8193);          // measured crossover: a single round of the per-envelope chains (<= 8192 envelopes) is faster than the batch check (profiles/r04_verify_g16_batch.json)
+        const int rlc_min = g16_rlc_min();
         if (rlc_min > 0 && n >= (uint64_t)rlc_min && !getenv("ZKP_HIP_NO_BATCH_VERIFY")) {
             const uint32_t n_ic = K.vk.n_ic;
             uint8_t* d_rlc = nullptr;
@@ -752,6 +755,20 @@ int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride
     if (rc) return rc;
     quiesce.armed = false;
     return 0;
+}
+
+// The same over the registered shards that hold a usable key of `kind` when the plan of verify_shards.h says so (*fanned), one slice per
+// shard through verify_g16_host: every slice draws its own weights and makes its own batch check.  A caller's shard without the key: not
+// fanned, and the usual path reports the missing key.  Minimum slice: the batch-check threshold in force (ZKP_HIP_G16_BATCH_VERIFY_MIN).
+int verify_g16_fanned(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok, bool* fanned) {
+    *fanned = false;
+    const std::vector<Device*> shards = verify_fanout_candidates();
+    if (shards.empty()) return 0;
+    std::vector<uint8_t> holds(shards.size());
+    for (size_t k = 0; k < shards.size(); k++) { std::lock_guard<std::mutex> lk(shards[k]->mu); holds[k] = shards[k]->g16 && shards[k]->g16->key[kind].vk_ready; }
+    const int rlc_min = g16_rlc_min();
+    return verify_fan_out(shards, holds.data(), n, nullptr, 1u, rlc_min > 0 ? (uint64_t)rlc_min : 8193u,
+                          [&](uint64_t lo, uint64_t m) { return verify_g16_host(kind, m, proofs + stride * lo, stride, lens + lo, ok + lo); }, fanned);
 }
 
 }  // namespace
@@ -822,14 +839,24 @@ int zkp_hip_groth16_generate_key(int kind, const uint8_t* setup_seed, uint8_t* p
 
 int zkp_hip_verify_equality_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc || (rc = bind.open())) return rc;
+    int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc) return rc;
+    bool fanned = false;
+    rc = verify_g16_fanned(G16_EQUALITY, n, proofs, stride, lens, ok, &fanned);
+    if (rc || fanned) return rc;
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return verify_g16_host(G16_EQUALITY, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 int zkp_hip_verify_membership_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    Bind bind; int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc || (rc = bind.open())) return rc;
+    int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    if (rc) return rc;
+    bool fanned = false;
+    rc = verify_g16_fanned(G16_MEMBERSHIP, n, proofs, stride, lens, ok, &fanned);
+    if (rc || fanned) return rc;
+    Bind bind;
+    if ((rc = bind.open())) return rc;
     return verify_g16_host(G16_MEMBERSHIP, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 

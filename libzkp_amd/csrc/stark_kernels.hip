@@ -26,6 +26,11 @@ __global__ void __launch_bounds__(64) k_stark_verify(const uint8_t* in, uint64_t
     const uint32_t l = len[i] <= stride ? len[i] : 0u;
     ok[i] = stark_verify_envelope(in + (uint64_t)i * stride, l, oldv[i], *C) ? 1 : 0;
 }
+uint32_t stark_verify_blocks_per_cu() {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_stark_verify, 64, 0) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return occ > 0 ? (uint32_t)occ : 0;
+}
 void stark_launch_verify(const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, const uint64_t* d_old, uint32_t n, const StarkConst* d_const, uint8_t* d_ok, hipStream_t st) {
     if (n) k_stark_verify<<<(n + 63) / 64, 64, 0, st>>>(d_in, stride, d_len, d_old, n, d_const, d_ok);
 }

@@ -37,6 +37,7 @@
 #include "bpv_launch.h"
 #include "edg_launch.h"
 #include "batch_self_check.h"
+#include "verify_shards.h"
 #include "../../include/libzkp_hip.h"
 
 // ================================================================================================ kernels
@@ -338,6 +339,9 @@ struct Device {
     struct G16VerifyStats { double ms = 0; uint64_t launches = 0, adds = 0; } g16_verify;
     // ZKP_HIP_COUNTER_BATCH_SELF_CHECK, always counted: ops verified / refused by the self-check of flagged batches, host ms from the end of proving (batch_impl.inc: self_check_shard)
     struct SelfCheckStats { double ms = 0; uint64_t verified = 0, refused = 0; } self_check;
+    // ZKP_HIP_COUNTER_VERIFY_FANOUT, always counted: slices of fanned-out verify calls run on this shard and their envelopes; host ms of those calls on the caller's shard (verify_fan_out)
+    struct VerifyFanoutStats { double ms = 0; uint64_t slices = 0, envelopes = 0; } verify_fanout;
+    uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
 };
@@ -387,6 +391,7 @@ struct Registry {
 Registry& registry() { static Registry* r = new Registry(); return *r; }
 thread_local Device* t_dev = nullptr;      // shard the calling thread is bound to for the duration of an ABI call
 thread_local int t_sel = 0;                // shard the per-variant entry points of this thread use (zkp_hip_use_device)
+thread_local bool t_sel_chosen = false;    // this thread has called zkp_hip_use_device: it does its own splitting, its verify calls stay on t_sel (verify_fan_out)
 Device& dev() { return *t_dev; }
 DevPool& dev_pool() { return dev().pool; }
 void dev_scope_quiesce() { if (dev().stream) (void)hipStreamSynchronize(dev().stream); }
@@ -821,6 +826,47 @@ template <class F> int for_each_device(const std::vector<Device*>& devs, F f, bo
     return any;
 }
 
+// ---- One zkp_hip_verify_*_batch call over every registered shard (plan and rules: verify_shards.h).  The entry points call these after
+// argument validation and BEFORE any Bind: a thread that held its shard while posting to that shard's worker would wait for itself.
+// The shards a call may spread over -- empty (the call stays on the caller's shard, as before) when one shard is registered, when
+// ZKP_HIP_VERIFY_SHARDS=0, or when this thread has selected a shard with zkp_hip_use_device: callers that run one host thread per GPU do
+// their own splitting and must not post to each other's shards.  Read on every call.
+std::vector<Device*> verify_fanout_candidates() {
+    std::vector<Device*> shards;
+    if (t_sel_chosen || env_int("ZKP_HIP_VERIFY_SHARDS", 1) == 0) return shards;
+    Registry& R = registry();
+    std::lock_guard<std::mutex> lk(R.mu);
+    if (R.shards.size() > 1) shards.assign(R.shards.begin(), R.shards.begin() + std::min<size_t>(R.shards.size(), VS_MAX_SHARDS));
+    return shards;
+}
+// Cuts n envelopes (weights: verify_shards.h) over the shards of `shards` that hold what the scheme needs (`holds`, one flag per shard;
+// nullptr: all) and runs slice(lo, m) -- the scheme's host-buffer verifier on the envelopes [lo, lo + m) -- bound to each slice's shard, on
+// the shards' workers.  min_jobs: the scheme's batch-check threshold in force; ZKP_HIP_VERIFY_SHARD_MIN=<jobs> replaces it for every
+// scheme (read on every call).  *fanned = false and 0 returned when the plan is one slice: the caller then takes its usual path.  A negative
+// code of any slice fails the call with that slice's message (for_each_device).
+template <class F> int verify_fan_out(const std::vector<Device*>& shards, const uint8_t* holds, uint64_t n, const uint64_t* prefix, uint32_t unit, uint64_t min_jobs,
+                                      F slice, bool* fanned) {
+    *fanned = false;
+    uint32_t part[VS_MAX_SHARDS]; uint64_t bounds[VS_MAX_SHARDS + 1];
+    const uint32_t np = vs_participants((uint32_t)t_sel, (uint32_t)shards.size(), holds, part);
+    if (np < 2) return 0;
+    const int forced = env_int("ZKP_HIP_VERIFY_SHARD_MIN", 0);
+    const uint32_t count = vs_plan(n, prefix, unit, np, forced > 0 ? (uint64_t)forced : min_jobs, bounds);
+    if (count < 2) return 0;
+    *fanned = true;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<Device*> devs(count);
+    for (uint32_t k = 0; k < count; k++) devs[k] = shards[part[k]];
+    const int rc = for_each_device(devs, [&](size_t k) {
+        Device::VerifyFanoutStats& T = dev().verify_fanout;
+        T.slices++; T.envelopes += bounds[k + 1] - bounds[k];
+        return slice(bounds[k], bounds[k + 1] - bounds[k]);
+    });
+    std::lock_guard<std::mutex> lk(devs[0]->mu);
+    devs[0]->verify_fanout.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
 // workspace carving ---------------------------------------------------------------------------------
 struct Ws {
     JobBuf J; BpView V; CtView T;
@@ -1202,7 +1248,7 @@ int zkp_hip_device_count(void) try { Registry& R = registry(); std::lock_guard<s
 int zkp_hip_use_device(int shard) try {
     Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu);
     if (shard < 0 || (shard > 0 && shard >= (int)R.shards.size())) return fail(ZKP_HIP_E_ARGUMENT, "zkp_hip_use_device: no such shard");
-    t_sel = shard;
+    t_sel = shard; t_sel_chosen = true;
     return 0;
 } ZKP_API_CATCH_INT
 
@@ -1212,7 +1258,7 @@ int zkp_hip_use_device(int shard) try {
 void zkp_hip_shutdown(void) try {
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards.swap(R.shards); }
-    t_sel = 0;
+    t_sel = 0; t_sel_chosen = false;
     for (Device* d : shards) {
         std::lock_guard<std::mutex> lk(d->mu);
         if (!d->ready) continue;
@@ -1233,6 +1279,7 @@ void zkp_hip_shutdown(void) try {
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
         d->g16_verify = Device::G16VerifyStats();
         d->self_check = Device::SelfCheckStats();
+        d->verify_fanout = Device::VerifyFanoutStats(); d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
@@ -1247,7 +1294,7 @@ void zkp_hip_profile_enable(int on) try {
 
 // accumulated over all shards
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset) try {
-    if (which < 0 || which > ZKP_HIP_COUNTER_BATCH_SELF_CHECK) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
+    if (which < 0 || which > ZKP_HIP_COUNTER_VERIFY_FANOUT) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
@@ -1264,6 +1311,13 @@ int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint6
             Device::SelfCheckStats& V = d->self_check;
             tms += V.ms; tl += V.verified; ta += V.refused;
             if (reset) V = Device::SelfCheckStats();
+            continue;
+        }
+        if (which == ZKP_HIP_COUNTER_VERIFY_FANOUT) {
+            std::lock_guard<std::mutex> dl(d->mu);
+            Device::VerifyFanoutStats& V = d->verify_fanout;
+            tms += V.ms; tl += V.slices; ta += V.envelopes;
+            if (reset) V = Device::VerifyFanoutStats();
             continue;
         }
         Bind bind; int rc = bind.open(d);

@@ -30,6 +30,7 @@ pub const OP_SELF_CHECK: u32 = 0x100;
 pub const ZKP_HIP_COUNTER_G16_VERIFY: c_int = 3;
 /// `zkp_hip_profile_read_kernel` id (not a kernel): ops verified / ops refused / host ms of the self-check of flagged batches.
 pub const ZKP_HIP_COUNTER_BATCH_SELF_CHECK: c_int = 4;
+pub const ZKP_HIP_COUNTER_VERIFY_FANOUT: c_int = 5;
 
 /// `zkp_hip_op`: one BatchOperation (utils/composition.rs:343-350) flattened; `kind` = the envelope scheme id.
 #[repr(C)]
