@@ -330,7 +330,11 @@ enum { ZKP_HIP_KERNEL_MSM_ED25519 = 0, ZKP_HIP_KERNEL_MSM_BN254_G1 = 1, ZKP_HIP_
        /* Not a kernel: zkp_hip_verify_*_batch calls that were spread over several shards (see "Verification over every registered GPU" above).
         * Always counted, per shard, summed over the shards, same `reset`.  *launches = slices run by fanned-out calls; *point_adds = envelopes in
         * those slices; *ms = host wall time of the fanned-out calls, measured in the calling thread.  A call that stayed on one shard counts nothing. */
-       ZKP_HIP_COUNTER_VERIFY_FANOUT = 5 };
+       ZKP_HIP_COUNTER_VERIFY_FANOUT = 5,
+       /* Not a kernel: the mixed verifier (libzkp_hip_verify.h: zkp_hip_verify_envelopes / _device).  Always counted, per shard, summed over the
+        * shards, same `reset`.  *launches = scheme passes run (one per scheme that had rows, per call or slice); *point_adds = envelopes that got
+        * a row (everything the classification did not reject); *ms = host wall time of the calls on their shards. */
+       ZKP_HIP_COUNTER_VERIFY_MIXED = 6 };
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset);
 int zkp_hip_profile_read(double* msm_ms, uint64_t* msm_launches, uint64_t* msm_point_adds, int reset);
 /* Tunable (benchmarking).  window budget: 0 = chunking chosen per launch from the batch size (default); 32*T = slot-aligned

@@ -14,6 +14,7 @@ TABLES_BP_GENERATORS = 2          # zkp_hip_groth16_key_info kind: the Bulletpro
 COUNTER_G16_VERIFY = 3            # zkp_hip_profile_read_kernel id: what the Groth16 verifier did after failed batch checks (include/libzkp_hip.h)
 COUNTER_BATCH_SELF_CHECK = 4      # zkp_hip_profile_read_kernel id: ops verified / refused by the self-check of flagged batches (include/libzkp_hip.h)
 COUNTER_VERIFY_FANOUT = 5         # zkp_hip_profile_read_kernel id: slices / envelopes / host ms of verify calls spread over several shards (include/libzkp_hip.h)
+COUNTER_VERIFY_MIXED = 6          # zkp_hip_profile_read_kernel id: scheme passes / envelopes with a row / host ms of the mixed verifier (include/libzkp_hip.h)
 OP_SELF_CHECK = 0x100             # ZKP_HIP_OP_SELF_CHECK: OR-ed into the kind of every op of a batch that verifies its own proofs before release
 # symbols declared in include/libzkp_hip.h (checked by tests/test_abi.py)
 EXPORTS = (
@@ -26,6 +27,8 @@ EXPORTS = (
     "zkp_hip_init_devices", "zkp_hip_device_count", "zkp_hip_use_device", "zkp_hip_process_batch_bytes", "zkp_hip_batch_stage", "zkp_hip_batch_prove", "zkp_hip_batch_max_bytes",
     "zkp_hip_batch_fetch", "zkp_hip_batch_free", "zkp_hip_profile_read_kernel", "zkp_hip_batch_device_results", "zkp_hip_plan_shards", "zkp_hip_batch_prove_async", "zkp_hip_batch_wait",
 )
+# symbols declared in include/libzkp_hip_verify.h (checked by tests/test_abi_verify.py)
+EXPORTS_VERIFY = ("zkp_hip_verify_envelopes", "zkp_hip_verify_envelopes_device")
 
 _lib = None
 
@@ -113,6 +116,9 @@ def lib():
         L.zkp_hip_verify_membership_batch.restype = ctypes.c_int
         L.zkp_hip_verify_improvement_batch.argtypes = [u64, vp, u64, vp, vp, vp]
         L.zkp_hip_verify_improvement_batch.restype = ctypes.c_int
+        for f in (L.zkp_hip_verify_envelopes, L.zkp_hip_verify_envelopes_device):
+            f.argtypes = [u64, vp, vp, vp, vp]
+            f.restype = ctypes.c_int
         L.zkp_hip_process_batch.argtypes = [u64, vp, vp, vp, vp, u64, vp, vp]
         L.zkp_hip_process_batch.restype = ctypes.c_int
         L.zkp_hip_profile_enable.argtypes = [ctypes.c_int]

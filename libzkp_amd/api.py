@@ -564,6 +564,42 @@ def verify_fanout_counters(reset=True):
     return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
 
 
+def verify_mixed_counters(reset=True):
+    """What the mixed verifier (verify_envelopes, and through it verify_proofs_parallel / verify_composite_proof) did, summed over the shards
+    since the last reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_VERIFY_MIXED; always counted): {"launches": scheme passes run,
+    "point_adds": envelopes that got a row (everything the classification did not reject), "ms": host wall time of the calls}.
+    reset=True zeroes the counters."""
+    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_VERIFY_MIXED, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
+                  "zkp_hip_profile_read_kernel")
+    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+
+
+def verify_envelopes(envelopes, expect=None):
+    """verify_single_proof (performance.rs:270-293) for a list of envelopes of any scheme in ONE library call (zkp_hip_verify_envelopes,
+    include/libzkp_hip_verify.h): list of bools in the caller's order.  expect: None, or per envelope 0 ("any scheme") or the scheme id
+    the envelope must carry.  Every parameter (bounds, threshold, old value, embedded set) is the envelope's own.  Never raises on
+    malformed envelopes (they are False)."""
+    blobs = [bytes(e) for e in envelopes]
+    n = len(blobs)
+    if expect is not None and len(expect) != n:
+        raise ValueError("envelopes, expect must have equal length")
+    if n == 0:
+        return []
+    for kind, scheme in ((0, 2), (1, 4)):              # a Groth16 key only for the circuits whose scheme byte occurs
+        if any(len(b) > 1 and b[1] == scheme for b in blobs):
+            _ensure_key(kind, verifier=True)
+    blob = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(b) for b in blobs), dtype=np.uint64, count=n), out=off[1:])
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    ex = None if expect is None else np.ascontiguousarray(np.asarray(expect, dtype=np.uint8))
+    ok = np.zeros(n, dtype=np.uint8)
+    _native.check(_native.lib().zkp_hip_verify_envelopes(n, _P(blob), _P(off), None if ex is None else _P(ex), _P(ok)), "zkp_hip_verify_envelopes")
+    return (ok == 1).tolist()
+
+
 def verify_equality_with_commitment_batch(proofs, commitments):
     """Batched verify_equality_with_commitment (equality_proof.rs:34-60): the envelope must carry exactly that commitment."""
     blobs = [bytes(p) for p in proofs]

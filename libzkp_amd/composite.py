@@ -9,7 +9,8 @@
                                     /root/reference/src/utils/performance.rs:251-293, utils/proof_helpers.rs:156-247
 
 Pure host-side framing (SHA-256, length-prefixed fields) around proofs that the GPU produces and verifies; the
-cryptographic checks go through libzkp_amd.api's batched GPU verifiers (Bulletproofs family, STARK, Groth16 pairing check).
+cryptographic checks go through libzkp_amd.api.verify_envelopes, the library's one call for a list of envelopes of any scheme
+(Bulletproofs family, STARK, Groth16 pairing check).
 Error mapping as in api.py: InvalidInput -> ValueError, InvalidProofFormat -> TypeError (error_handling.rs:39-50)."""
 import hashlib
 
@@ -136,50 +137,10 @@ def verify_composite_proof_integrity_only(composite_bytes):
 
 
 def verify_proof_cryptographic_batch(envelopes):
-    """verify_proof_cryptographic for a list of envelopes, one batched GPU call per scheme (proof_helpers.rs:156-247)."""
+    """verify_proof_cryptographic for a list of envelopes (proof_helpers.rs:156-247): one library call for all schemes
+    (api.verify_envelopes: the parsing, the pre-checks and the sorting by scheme happen on the GPU)."""
     from . import api
-    out = [False] * len(envelopes)
-    groups = {1: [], 2: [], 3: [], 4: [], 5: [], 6: []}
-    for i, env in enumerate(envelopes):
-        try:
-            version, scheme, payload, commitment = parse_proof(env)
-        except ProofFormatError:
-            continue
-        if version != PROOF_VERSION:
-            continue
-        if scheme == 2 and len(commitment) == 32:
-            groups[2].append((i, env))
-        elif scheme == 4 and len(commitment) == 32 and len(payload) > 4:
-            groups[4].append((i, env))
-        elif scheme == 1 and len(payload) >= 20 and len(commitment) == 32:
-            mn, mx = int.from_bytes(payload[:8], "little"), int.from_bytes(payload[8:16], "little")
-            if mn <= mx:
-                groups[1].append((i, env, mn, mx))
-        elif scheme == 3 and len(payload) >= 12 and len(commitment) == 32:
-            groups[3].append((i, env, int.from_bytes(payload[:8], "little")))
-        elif scheme == 5 and len(payload) >= 16 and len(commitment) == 32:
-            groups[5].append((i, env, int.from_bytes(payload[:8], "little")))
-        elif scheme == 6:
-            groups[6].append((i, env))
-    if groups[1]:
-        for (i, *_), ok in zip(groups[1], api.verify_range_batch([g[1] for g in groups[1]], [g[2] for g in groups[1]], [g[3] for g in groups[1]])):
-            out[i] = ok
-    if groups[2]:
-        for (i, *_), ok in zip(groups[2], api._verify_snark_envelopes(0, [g[1] for g in groups[2]])):
-            out[i] = ok
-    if groups[4]:
-        for (i, *_), ok in zip(groups[4], api._verify_snark_envelopes(1, [g[1] for g in groups[4]])):
-            out[i] = ok
-    if groups[3]:
-        for (i, *_), ok in zip(groups[3], api.verify_threshold_batch([g[1] for g in groups[3]], [g[2] for g in groups[3]])):
-            out[i] = ok
-    if groups[5]:
-        for (i, *_), ok in zip(groups[5], api.verify_improvement_batch([g[1] for g in groups[5]], [g[2] for g in groups[5]])):
-            out[i] = ok
-    if groups[6]:
-        for (i, *_), ok in zip(groups[6], api.verify_consistency_batch([g[1] for g in groups[6]])):
-            out[i] = ok
-    return out
+    return api.verify_envelopes(envelopes)
 
 
 def verify_composite_proof(composite_bytes):
@@ -189,17 +150,9 @@ def verify_composite_proof(composite_bytes):
 
 def verify_proofs_parallel(proofs):
     """[(proof bytes, type name)] -> [bool]: the type must match the envelope's scheme id (performance.rs:269-293)."""
-    idx, envs, out = [], [], [False] * len(proofs)
-    for i, (data, name) in enumerate(proofs):
-        try:
-            version, scheme, _, _ = parse_proof(data)
-        except ProofFormatError:
-            continue
-        if version == PROOF_VERSION and SCHEME_BY_NAME.get(name) == scheme:
-            idx.append(i); envs.append(bytes(data))
-    for i, ok in zip(idx, verify_proof_cryptographic_batch(envs)):
-        out[i] = ok
-    return out
+    from . import api
+    # an unknown type name matches no scheme id: 255 is not one, and any expected value other than 0 and the envelope's own rejects
+    return api.verify_envelopes([bytes(data) for data, _ in proofs], [SCHEME_BY_NAME.get(name, 255) for _, name in proofs])
 
 
 def validate_proof_chain(proof_chain):

@@ -133,15 +133,11 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
     return 0;
 }
 
-// jobs of each consistency envelope, read from its own k field (k - 1 range proofs; 0 for an envelope the device step will reject)
+// jobs of each consistency envelope, read from its own k field (k - 1 range proofs; 0 for an envelope the device step will reject): the rule
+// is ve_consistency_jobs (venv_steps.h), shared with the mixed verifier's classification kernel
 std::vector<uint32_t> consistency_job_counts(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens) {
     std::vector<uint32_t> job_counts(n);
-    for (uint64_t i = 0; i < n; i++) {
-        const uint8_t* env = proofs + stride * i; uint64_t k = 0;
-        if (lens[i] <= stride && lens[i] >= 14) k = (uint64_t)env[10] | ((uint64_t)env[11] << 8) | ((uint64_t)env[12] << 16) | ((uint64_t)env[13] << 24);
-        const bool fits = k >= 1 && k < (1u << 20) && 10 + 4 + 32 * k + (uint64_t)(4 + RP_BYTES + 32) * (k - 1) + 32 <= lens[i];
-        job_counts[i] = fits ? (uint32_t)(k - 1) : 0u;       // the device step rejects an envelope whose k disagrees
-    }
+    for (uint64_t i = 0; i < n; i++) job_counts[i] = lens[i] <= stride ? ve_consistency_jobs(proofs + stride * i, lens[i]) : 0u;
     return job_counts;
 }
 // the host-buffer entry points: upload, then the core above (the consistency job counts are read from the envelopes' own k fields)

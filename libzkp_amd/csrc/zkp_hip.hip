@@ -38,7 +38,8 @@
 #include "edg_launch.h"
 #include "batch_self_check.h"
 #include "verify_shards.h"
-#include "../../include/libzkp_hip.h"
+#include "venv_steps.h"
+#include "../../include/libzkp_hip_verify.h"
 
 // ================================================================================================ kernels
 
@@ -341,6 +342,8 @@ struct Device {
     struct SelfCheckStats { double ms = 0; uint64_t verified = 0, refused = 0; } self_check;
     // ZKP_HIP_COUNTER_VERIFY_FANOUT, always counted: slices of fanned-out verify calls run on this shard and their envelopes; host ms of those calls on the caller's shard (verify_fan_out)
     struct VerifyFanoutStats { double ms = 0; uint64_t slices = 0, envelopes = 0; } verify_fanout;
+    // ZKP_HIP_COUNTER_VERIFY_MIXED, always counted: scheme passes run by the mixed verifier on this shard, envelopes that got a row, host ms of its calls (venv_impl.inc)
+    struct VerifyMixedStats { double ms = 0; uint64_t passes = 0, rows = 0; } verify_mixed;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -1204,6 +1207,7 @@ int frame_consistency(uint64_t n, const uint64_t* data, const uint32_t* counts, 
 #include "g16_impl.inc"
 #include "stark_impl.inc"
 #include "bpv_impl.inc"
+#include "venv_impl.inc"
 
 // ================================================================================================ C ABI
 extern "C" {
@@ -1279,7 +1283,7 @@ void zkp_hip_shutdown(void) try {
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
         d->g16_verify = Device::G16VerifyStats();
         d->self_check = Device::SelfCheckStats();
-        d->verify_fanout = Device::VerifyFanoutStats(); d->stark_verify_resident = 0;
+        d->verify_fanout = Device::VerifyFanoutStats(); d->verify_mixed = Device::VerifyMixedStats(); d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
@@ -1294,7 +1298,7 @@ void zkp_hip_profile_enable(int on) try {
 
 // accumulated over all shards
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset) try {
-    if (which < 0 || which > ZKP_HIP_COUNTER_VERIFY_FANOUT) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
+    if (which < 0 || which > ZKP_HIP_COUNTER_VERIFY_MIXED) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
@@ -1318,6 +1322,13 @@ int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint6
             Device::VerifyFanoutStats& V = d->verify_fanout;
             tms += V.ms; tl += V.slices; ta += V.envelopes;
             if (reset) V = Device::VerifyFanoutStats();
+            continue;
+        }
+        if (which == ZKP_HIP_COUNTER_VERIFY_MIXED) {
+            std::lock_guard<std::mutex> dl(d->mu);
+            Device::VerifyMixedStats& V = d->verify_mixed;
+            tms += V.ms; tl += V.passes; ta += V.rows;
+            if (reset) V = Device::VerifyMixedStats();
             continue;
         }
         Bind bind; int rc = bind.open(d);

@@ -4,6 +4,7 @@
 //! both behind a `hip` cargo feature, and route the call sites listed in INTEGRATION.md section 2 here.  Signatures,
 //! empty-vector-on-failure and `Result<_, String>` conventions are those of the CPU backends they replace.
 use super::hip_ffi as ffi;
+use super::hip_ffi_verify as ffi_verify;
 use super::ZkpBackend;
 use crate::utils::composition::BatchOperation;
 use crate::utils::error_handling::{ZkpError, ZkpResult};
@@ -256,4 +257,56 @@ pub fn process_batch_operations(ops: &[BatchOperation], self_check: bool) -> Zkp
         return Err(to_zkp_error((st[i], format!("batch operation {} failed with status {}", i, st[i]))));
     }
     Ok((0..n).map(|i| out[off[i] as usize..off[i + 1] as usize].to_vec()).collect())
+}
+
+/// One FFI call for a list of envelopes of any scheme (include/libzkp_hip_verify.h): the parsing, `verify_proof_cryptographic`'s
+/// pre-checks, the sorting by scheme and the verifiers all run on the GPU; no bucketing on the host.  `expect`: one byte per envelope
+/// (`EXPECT_ANY`, a scheme id, or `EXPECT_NONE`), or empty for "any" throughout.  A failed call (no device, a missing Groth16 key)
+/// verifies nothing: every verdict is false, as the CPU verifiers answer when their backend errors.
+fn verify_envelope_list(envelopes: &[&[u8]], expect: &[u8]) -> Vec<bool> {
+    let n = envelopes.len();
+    if n == 0 {
+        return vec![];
+    }
+    let mut off = Vec::with_capacity(n + 1);
+    let mut blob = Vec::with_capacity(envelopes.iter().map(|e| e.len()).sum::<usize>() + 1);
+    off.push(0u64);
+    for e in envelopes {
+        blob.extend_from_slice(e);
+        off.push(blob.len() as u64);
+    }
+    blob.push(0); // keeps the pointer non-null for a list of empty envelopes; outside [off[0], off[n]), never read
+    let mut ok = vec![0u8; n];
+    let ex = if expect.is_empty() { std::ptr::null() } else { expect.as_ptr() };
+    let rc = unsafe { ffi_verify::zkp_hip_verify_envelopes(n as u64, blob.as_ptr(), off.as_ptr(), ex, ok.as_mut_ptr()) };
+    if rc != 0 {
+        return vec![false; n];
+    }
+    ok.iter().map(|&v| v == 1).collect()
+}
+
+/// utils::performance::verify_proofs_parallel (performance.rs:251-293): `(proof bytes, type name)` pairs; the type must name the
+/// envelope's scheme.  Replaces the rayon map over `verify_single_proof`.
+pub fn verify_proofs_parallel(proofs: &[(Vec<u8>, String)]) -> Vec<bool> {
+    let expect: Vec<u8> = proofs
+        .iter()
+        .map(|(_, name)| match name.as_str() {
+            "range" => 1,
+            "equality" => 2,
+            "threshold" => 3,
+            "membership" => 4,
+            "improvement" => 5,
+            "consistency" => 6,
+            _ => ffi_verify::EXPECT_NONE,
+        })
+        .collect();
+    let envs: Vec<&[u8]> = proofs.iter().map(|(p, _)| p.as_slice()).collect();
+    verify_envelope_list(&envs, &expect)
+}
+
+/// advanced::composite::verify_composite_proof (composite.rs:25-35) after `CompositeProof::from_bytes`: every inner proof must pass
+/// `verify_proof_cryptographic`.  `inner`: the serialized inner proofs (`Proof::to_bytes`), in the composite's order.
+pub fn verify_composite_inner_proofs(inner: &[Vec<u8>]) -> bool {
+    let envs: Vec<&[u8]> = inner.iter().map(|p| p.as_slice()).collect();
+    verify_envelope_list(&envs, &[]).iter().all(|&v| v)
 }
