@@ -41,7 +41,8 @@ template <class P> ZKP_HD inline Fp<P> fp_const_r3() { Fp<P> r; ZKP_UNROLL for (
         ZKP_UNROLL for (int i_ = 0; i_ < 8; i_++) (out_).v[i_] = br_ ? (t_)[i_] : d_[i_];          \
     } while (0)
 
-// a * b * 2^-256 ; inputs < 2p (or a < 2^256 with b < p), output < 2p
+// a * b * 2^-256 ; inputs < 2p (or a < 2^256 with b < p and every word of b below 2^32 - 2, as the words of r2 and r3 are: a row's carry
+// is up to b's word + 1 there, and t8 below holds it plus t[8] in 32 bits), output < 2p
 template <class P> ZKP_HD inline Fp<P> fp_mul(const Fp<P>& a, const Fp<P>& b) {
     uint32_t t[9];
     ZKP_UNROLL for (int i = 0; i < 9; i++) t[i] = 0;

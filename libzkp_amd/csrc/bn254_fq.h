@@ -7,7 +7,8 @@
 //
 // Bounds vocabulary (checked by tests/test_fq_bounds.py):
 //   carried : limbs 0..8 < 2^26 (limb 9 holds the rest);   safe : carried and value < 4p
-//   fq_mul / fq_sq accept limbs < 2^29 and return a carried value < A*B/(84.6 p) + p   (p/R = 1/84.6)
+//   fq_mul / fq_sq accept limbs < 2^29 and return a carried value < A*B/(84.6 p) + p   (p/R = 1/84.6); the VALUES must keep that
+//   result below 4p (A*B < 253 p^2): ten limbs of 2^29 - 1 are the value 677 p, whose square leaves a top limb past 32 bits
 //   fq_add_l / fq_sub_k* are limb-wise (no carries); fq_sub_kN adds N*p in a borrowed form whose low limbs are >= 2^(24+log2 N)
 //   fq_reduce_weak brings any value < 2^260 to [0, 3p), carried.
 #pragma once
@@ -103,7 +104,7 @@ ZKP_HD inline fq fq_sub_k4(const fq& a, const fq& b) { fq r; ZKP_UNROLL for (int
 ZKP_HD inline fq fq_sub_k8(const fq& a, const fq& b) { fq r; ZKP_UNROLL for (int i = 0; i < 10; i++) r.v[i] = a.v[i] + fq_k8(i) - b.v[i]; return r; }     // b: low limbs <= 2^27, value < 8p
 ZKP_HD inline fq fq_sub_k16(const fq& a, const fq& b) { fq r; ZKP_UNROLL for (int i = 0; i < 10; i++) r.v[i] = a.v[i] + fq_k16(i) - b.v[i]; return r; }   // b: low limbs <= 2^28, value < 16p
 
-// limb normalisation (value unchanged); input limbs < 2^32, value < 2^260
+// limb normalisation (value unchanged); input limbs < 2^32 - 2^6 (the carry into a limb must not wrap it), value < 2^260
 ZKP_HD inline fq fq_carry(const fq& a) {
     fq r; uint32_t c = 0;
     ZKP_UNROLL for (int i = 0; i < 9; i++) { const uint32_t t = a.v[i] + c; r.v[i] = t & ZKP_FQ_MASK; c = t >> 26; }

@@ -128,7 +128,8 @@ ZKP_HD inline g1_xyzz g1_mmadd_lazy(const g1_xyzz& p, const Aff<fq>& q) {
     return r;
 }
 // The same addition on nine 29-bit limbs (bn254_fq9.h), the form k_msm_gather<G1Msm> runs in.  Value bounds in units of p, every
-// operand carried9: accumulator X < 8, Y < 4, ZZ, ZZZ < 2; table entry x, y < 4.  U2, S2 < 4*2/169+1 = 1.05; P < 9.05, R < 5.05;
+// operand carried9: accumulator X < 8, Y < 3 (fq9_neg_loose<4> takes no borrow into the top limb: Y within 2^232 of 4p would wrap it), ZZ, ZZZ < 2;
+// table entry x, y < 4.  U2, S2 < 4*2/169+1 = 1.05; P < 9.05, R < 5.05;
 // PP < 1.49, PPP < 1.08, Q < 1.08, RR < 1.16; X3 < 5.16; Y3 < (5.05*9.08 + 4*1.08)/169 + 1 = 1.30; ZZ3, ZZZ3 < 1.02.
 struct g1_xyzz9 { fq9 X, Y, ZZ, ZZZ; };
 struct g1_aff9 { fq9 x, y; };

@@ -12,3 +12,5 @@ void edg_launch_msm(const zkp::MsmView& m, uint32_t ngroups, uint32_t nblocks, h
 // counts mismatches
 void edg_launch_build(const zkp::EdgGeom& g, const uint32_t* d_gens, uint32_t* d_table, uint32_t* d_scratch, int* d_bad, hipStream_t st);
 size_t edg_build_scratch_words(const zkp::EdgGeom& g);
+// k_sum_t<EdMsm> (8 slices of 32 rows per 256-lane block), defined beside its kernel in zkp_hip.hip
+void edg_launch_sum(const zkp::ReduceView& R, uint32_t* sums, hipStream_t st);

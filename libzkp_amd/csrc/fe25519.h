@@ -58,7 +58,7 @@ ZKP_HD inline fe fe_mul(const fe& f, const fe& g) {
     return o;
 }
 
-// h = f^2 (55 products); f loose
+// h = f^2 (55 products); f with even limbs < 1.5*2^27, odd limbs < 1.5*2^26 like fe_mul's g (19*f must fit 32 bits: a loose f does not)
 ZKP_HD inline fe fe_sq(const fe& f) {
     uint32_t f19[10], f2[10], f4[10];
     ZKP_UNROLL for (int i = 0; i < 10; i++) { f19[i] = 19u * f.v[i]; f2[i] = 2u * f.v[i]; f4[i] = 4u * f.v[i]; }

@@ -1203,6 +1203,8 @@ int frame_consistency(uint64_t n, const uint64_t* data, const uint32_t* counts, 
 }
 
 }  // namespace
+// the ed25519 sum launcher under an external name (edg_launch.h): launch_sum_ed above has internal linkage
+void edg_launch_sum(const ReduceView& R, uint32_t* sums, hipStream_t st) { launch_sum_ed(R, sums, st); }
 
 #include "g16_impl.inc"
 #include "stark_impl.inc"

@@ -8,6 +8,14 @@ def carried():
     return [2**26 if i % 2 == 0 else 2**25 + 2**18 for i in range(10)]     # exclusive upper bounds
 
 
+def loose():
+    return [2**28 if i % 2 == 0 else 2**27 for i in range(10)]             # sums / differences of carried values; fe_mul's first operand
+
+
+def semi_loose():
+    return [3 * 2**26 if i % 2 == 0 else 3 * 2**25 for i in range(10)]     # fe_mul's second operand and fe_sq's operand: 19 * limb fits 32 bits
+
+
 def add(f, g):
     return [a + b for a, b in zip(f, g)]
 
@@ -75,7 +83,5 @@ def test_add_and_double_bounds():
 
 
 def test_loose_times_semi_loose_is_the_documented_limit():
-    loose = [2**28 if i % 2 == 0 else 2**27 for i in range(10)]
-    semi = [3 * 2**26 if i % 2 == 0 else 3 * 2**25 for i in range(10)]
-    mul(loose, semi)
-    sq(semi)
+    mul(loose(), semi_loose())
+    sq(semi_loose())

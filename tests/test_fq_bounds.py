@@ -224,6 +224,15 @@ def test_safe_ops_used_by_generic_point_formulas():
 
 
 # ---- the nine-limb form of the G1 MSM loop (bn254_fq9.h): operands are carried (limbs < 2^29), values tracked in units of p
+M29 = (1 << 29) - 1
+LOOSE8_LIMB = M29 + (1 << 30) - 1         # inclusive limb bound of Q - X3 + 8p (fq9_sub_loose<8>)
+LOOSE4_LIMB = (1 << 30) - 1               # inclusive limb bound of 4p - Y1 (fq9_neg_loose<4>)
+# value bounds of the MSM accumulators and table entries in units of p (exclusive), as the comments beside g1_mmadd9 / g2_mmadd9 give them;
+# ZZ, ZZZ < 3 covers the converted accumulator a chunk starts from
+G1_MMADD9_BOUNDS = {"X": 8, "Y": 3, "ZZ": 3, "ZZZ": 3, "qx": 4, "qy": 4}
+G2_MMADD9_BOUNDS = {"X": (104, 10), "Y": (4, 1), "ZZ": (3, 1), "ZZZ": (3, 1), "q": (3, 1)}
+
+
 def header_constants9():
     import os
     import re
@@ -243,7 +252,7 @@ def test_nine_limb_constants_and_column_sums():
     assert val(c["fq9_pl"]) == P and val(c["fq9_k2"]) == 2 * P and val(c["fq9_k4"]) == 4 * P and val(c["fq9_k8"]) == 8 * P
     assert all(x < 1 << 29 for name in ("fq9_pl", "fq9_k2", "fq9_k4", "fq9_k8", "fq9_r10") for x in c[name])
     assert val(c["fq9_r10"]) == (1 << 260) % P and (c["n0"] * P + 1) % (1 << 29) == 0
-    m29 = (1 << 29) - 1
+    m29 = M29
     # widest column of a product: 9 operand products + 9 reduction products + the carry of the column before
     col = 9 * m29 * m29 + 9 * m29 * max(c["fq9_pl"])
     assert col + (col >> 29) < 1 << 64
@@ -260,7 +269,7 @@ def test_nine_limb_constants_and_column_sums():
         fat = [c[name][0] + (1 << 29)] + [c[name][i] + (1 << 29) - 1 for i in range(1, 8)] + [c[name][8] - 1]
         assert val(fat) == k * P
         assert all(f >= m29 for f in fat[:8]) and all(f < 1 << 30 for f in fat) and fat[8] > 0       # a_i + fat_i - b_i >= 0 for carried a, b (limbs <= 2^29 - 1)
-    loose8, loose4 = m29 + (1 << 30) - 1, (1 << 30) - 1                                               # limbs of Q - X3 + 8p and of 4p - Y1
+    loose8, loose4 = LOOSE8_LIMB, LOOSE4_LIMB                                                         # limbs of Q - X3 + 8p and of 4p - Y1
     col_l = 9 * m29 * loose8 + 9 * loose4 * m29 + 9 * m29 * max(c["fq9_pl"])
     assert col_l + (col_l >> 29) < 1 << 64
     # the top limb of a loose difference stays positive: the VALUE Q - X3 + 8p is at least 8p - X3 > 2.8 p (X3 < 5.2 p, test below), and the
@@ -271,12 +280,12 @@ def test_nine_limb_constants_and_column_sums():
 
 
 def test_g1_mmadd9_is_closed_over_its_value_bounds():
-    """g1_mmadd9 (bn254_g.h) in units of p: accumulator X < 8, Y < 4, ZZ, ZZZ < 2 and entries < 4 give the same bounds back, every
+    """g1_mmadd9 (bn254_g.h) in units of p: accumulator X < 8, Y < 3, ZZ, ZZZ < 2 and entries < 4 give the same bounds back, every
     subtrahend is covered by the multiple of p added, and nothing comes near 2^261 = 169.28 p (so top limbs stay below 2^29)"""
     from fractions import Fraction as F
     rp = F(1 << 261, P)
     mul = lambda a, b: a * b / rp + 1  # noqa: E731
-    X, Y, ZZ, ZZZ, qx, qy = F(8), F(4), F(3), F(3), F(4), F(4)                 # ZZ, ZZZ < 3 covers the converted accumulator a chunk starts from
+    X, Y, ZZ, ZZZ, qx, qy = (F(G1_MMADD9_BOUNDS[k]) for k in ("X", "Y", "ZZ", "ZZZ", "qx", "qy"))
     U2, S2 = mul(qx, ZZ), mul(qy, ZZZ)
     assert X <= 8 and Y <= 4                                  # fq9_sub_k<8>(U2, X), fq9_sub_k<4>(S2, Y)
     Pv, Rv = U2 + 8, S2 + 4
@@ -286,7 +295,10 @@ def test_g1_mmadd9_is_closed_over_its_value_bounds():
     assert X3 < 8                                             # fq9_sub_k<8>(Q, X3), and the next iteration's X
     Y3 = (Rv * (Q + 8) + 4 * PPP) / rp + 1
     ZZ3, ZZZ3 = mul(ZZ, PP), mul(ZZZ, PPP)
-    assert Y3 < 4 and ZZ3 < 2 and ZZZ3 < 2
+    assert Y3 < Y and ZZ3 < 2 and ZZZ3 < 2
+    # fq9_neg_loose<4>(Y1) borrows nothing into its top limb (the fat form's is 4p's less one), so every Y inside the bound must have a top
+    # limb below 4p's -- Y < 4 is not enough: the values within 2^232 of 4p wrap it (found by tests/test_devtier_math.py at Y = 4p - 1)
+    assert (int(Y * P) - 1) >> 232 <= header_constants9()["fq9_k4"][8] - 1
     assert max(Pv, Rv, X3, Q + 8) < rp / 8
     # conversions: fq9_from_fq of a reduce_weak value (< 3p) starts inside the bounds; entries negated as 4p - y with y < 3p
     assert 3 < 4 and 3 <= X and 3 <= Y and 3 <= ZZ
@@ -303,7 +315,7 @@ def test_g2_mmadd9_is_closed_over_its_value_bounds():
     from fractions import Fraction as F
     rp = F(1 << 261, P)
     m2 = lambda a, b, c, d: (a * b + c * d) / rp + 1  # noqa: E731
-    X, Y, ZZ, ZZZ, q = F(104, 10), F(4), F(3), F(3), F(3)
+    X, Y, ZZ, ZZZ, q = (F(*G2_MMADD9_BOUNDS[k]) for k in ("X", "Y", "ZZ", "ZZZ", "q"))
     assert ZZ < 4 and ZZZ < 4                                   # nZZ1, nZZZ1 = 4p - .
     U2 = max(m2(q, ZZ, q, 4), m2(q, ZZ, q, ZZ)); S2 = max(m2(q, ZZZ, q, 4), m2(q, ZZZ, q, ZZZ))
     assert X < 16 and S2 + Y < 8                                # P = U2 - X + 16p ; R = +-S2 - Y + 8p
