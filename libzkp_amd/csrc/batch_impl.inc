@@ -575,30 +575,23 @@ int self_check_shard(ShardPlan& P) {
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, st));
     k_self_check_rows<<<(n + 255) / 256, 256, 0, st>>>(V);
     HIP_TRY(hipGetLastError());
-    auto lens = [&](uint32_t k) { return (const uint32_t*)(V.row_len + P.v_row0[k]); };
-    auto oks = [&](uint32_t k) { return V.row_ok + P.v_row0[k]; };
-    if (P.n_range && (rc = verify_bp_device(1, P.n_range, ar + P.a_range, RANGE_PROOF_BYTES, lens(ZKP_HIP_OP_RANGE), (const uint64_t*)(in + P.i_rmin), (const uint64_t*)(in + P.i_rmax),
-                                            oks(ZKP_HIP_OP_RANGE), nullptr, nullptr))) return rc;
-    if (P.n_thr && (rc = verify_bp_device(3, P.n_thr, ar + P.a_thr, P.v_stride[ZKP_HIP_OP_THRESHOLD], lens(ZKP_HIP_OP_THRESHOLD), (const uint64_t*)(in + P.i_thr), nullptr,
-                                          oks(ZKP_HIP_OP_THRESHOLD), nullptr, nullptr))) return rc;
-    if (P.n_con) {
-        std::vector<uint32_t> jobs(P.n_con);          // k - 1 range proofs for a framed list of k values (none for a list the framing refused)
-        for (uint32_t k = 0; k < P.n_con; k++) jobs[k] = P.con_lens[k] && P.con_counts[k] ? P.con_counts[k] - 1 : 0;
-        if ((rc = verify_bp_device(6, P.n_con, ar + P.a_con, P.stride_con, lens(ZKP_HIP_OP_CONSISTENCY), nullptr, nullptr, oks(ZKP_HIP_OP_CONSISTENCY), jobs.data(), nullptr))) return rc;
-    }
-    if (P.n_eq || P.n_mem) {
-        DevScope mem;
-        struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;      // as verify_g16_host: the chains' side streams
-        std::vector<uint8_t> h_ok(P.n_eq > P.n_mem ? P.n_eq : P.n_mem);      // the batch check's verdicts, read by its localisation pass
-        if (P.n_eq && (rc = verify_g16_core(G16_EQUALITY, P.n_eq, ar + P.a_eq, 298, lens(ZKP_HIP_OP_EQUALITY), oks(ZKP_HIP_OP_EQUALITY), h_ok.data(), mem, hipSuccess))) return rc;
-        if (P.n_mem && (rc = verify_g16_core(G16_MEMBERSHIP, P.n_mem, ar + P.a_mem, P.stride_mem, lens(ZKP_HIP_OP_MEMBERSHIP), oks(ZKP_HIP_OP_MEMBERSHIP), h_ok.data(), mem, hipSuccess))) return rc;
-        quiesce.armed = false;
-        if ((rc = ensure_mimc_dev())) return rc;
-        V.mimc_c = g16s().mimc_dev;
-        k_self_check_bind_g16<<<(P.n_eq + P.n_mem + 63) / 64, 64, 0, st>>>(V);
-        HIP_TRY(hipGetLastError());
-    }
-    if (P.n_imp && (rc = verify_stark_device(P.n_imp, ar + P.a_imp, STARK_MAX_ENVELOPE, lens(ZKP_HIP_OP_IMPROVEMENT), (const uint64_t*)(in + P.i_io), oks(ZKP_HIP_OP_IMPROVEMENT)))) return rc;
+    std::vector<uint32_t> jobs(P.n_con);          // k - 1 range proofs for a framed list of k values (none for a list the framing refused)
+    for (uint32_t k = 0; k < P.n_con; k++) jobs[k] = P.con_lens[k] && P.con_counts[k] ? P.con_counts[k] - 1 : 0;
+    SchemePass K[SC_KINDS];
+    for (uint32_t k = 0; k < SC_KINDS; k++) { K[k].n = P.v_rows[k]; K[k].rows = ar + P.v_base[k]; K[k].stride = P.v_stride[k]; K[k].lens = V.row_len + P.v_row0[k]; K[k].ok = V.row_ok + P.v_row0[k]; }
+    K[ZKP_HIP_OP_RANGE].p0 = (const uint64_t*)(in + P.i_rmin); K[ZKP_HIP_OP_RANGE].p1 = (const uint64_t*)(in + P.i_rmax);
+    K[ZKP_HIP_OP_THRESHOLD].p0 = (const uint64_t*)(in + P.i_thr);
+    K[ZKP_HIP_OP_IMPROVEMENT].p0 = (const uint64_t*)(in + P.i_io);
+    K[ZKP_HIP_OP_CONSISTENCY].jobs = jobs.data();
+    DevScope g16_scratch;
+    if ((rc = verify_scheme_passes(K, g16_scratch, nullptr, [&]() {          // behind the Groth16 passes: the proofs' public inputs against the staged values
+            const int brc = ensure_mimc_dev();
+            if (brc) return brc;
+            V.mimc_c = g16s().mimc_dev;
+            k_self_check_bind_g16<<<(P.n_eq + P.n_mem + 63) / 64, 64, 0, st>>>(V);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }))) return rc;
     k_batch_lens<<<(n + 255) / 256, 256, 0, st>>>(W);
     k_self_check_apply<<<(n + 255) / 256, 256, 0, st>>>(V, d_cnt);
     k_batch_scan<<<1, 1024, 0, st>>>(W);
@@ -607,8 +600,8 @@ int self_check_shard(ShardPlan& P) {
     uint32_t cnt[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    Device::SelfCheckStats& C = dev().self_check;
-    C.verified += cnt[0]; C.refused += cnt[1];
+    Device::HostCounter& C = dev().counter(ZKP_HIP_COUNTER_BATCH_SELF_CHECK);
+    C.a += cnt[0]; C.b += cnt[1];
     C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }

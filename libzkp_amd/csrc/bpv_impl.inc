@@ -1,14 +1,15 @@
-// Range-proof verification, host side of libzkp_hip (included by zkp_hip.hip).  Kernels: bpv_kernels.hip + the prover's
-// MSM / partial-sum / encode kernels.
+// Range, threshold and consistency verification, host side of libzkp_hip (included by zkp_hip.hip): the core on device pointers
+// (verify_bp_device), one slice of a host-buffer call (verify_bp_host) and the three entry points on verify_call.  Kernels: bpv_kernels.hip +
+// the prover's MSM / partial-sum / encode kernels.
 namespace {
 
 struct VfyState { void* buf = nullptr; size_t cap = 0; LayoutSet set; bool ready = false; };      // per shard (Device::vfy)
 VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy; }
 
 // The verifier on device pointers: n envelopes at `stride` bytes in d_proofs, d_lens[i] bytes used, verdicts into d_ok (device); waits for them.
-// scheme 1 (range: bounds = d_mins, d_maxs; two jobs per envelope), 3 (threshold: bounds = thresholds, d_maxs unused; one job) or
-// 6 (consistency: no bounds; job_counts[i] jobs for envelope i, a host array from the caller -- the host entry point counts k - 1 from each
-// envelope's own k field, the batch self-check knows its ops' list lengths; the device step rejects an envelope whose k disagrees).
+// scheme: ZKP_HIP_OP_RANGE (bounds = d_mins, d_maxs; two jobs per envelope), ZKP_HIP_OP_THRESHOLD (bounds = thresholds, d_maxs unused; one job)
+// or ZKP_HIP_OP_CONSISTENCY (no bounds; job_counts[i] jobs for envelope i, a host array from the caller -- the host entry point counts k - 1
+// from each envelope's own k field, the batch self-check knows its ops' list lengths; the device step rejects an envelope whose k disagrees).
 // The batch check (k_rlc_*), its fallback and its three switches are in here, so every caller gets the same verdicts.
 // ok_host (may be null): the verdicts are also copied there before the one wait that ends the call.
 int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t stride, const uint32_t* d_lens, const uint64_t* d_mins, const uint64_t* d_maxs, uint8_t* d_ok,
@@ -20,13 +21,14 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
         if ((rc = upload_set(S.set, targets_verify((uint8_t)dev().edg.nwin)))) return rc;      // round 4: the prover's tables in HBM (edg.h)
         S.ready = true;
     }
-    const uint32_t jobs_per = scheme == 1 ? 2u : 1u;
+    const bool consistency = scheme == ZKP_HIP_OP_CONSISTENCY;
+    const uint32_t jobs_per = scheme == ZKP_HIP_OP_RANGE ? 2u : 1u;
     std::vector<uint32_t> job_base;
-    if (scheme == 6) {
+    if (consistency) {
         job_base.resize(n + 1); job_base[0] = 0;
         for (uint64_t i = 0; i < n; i++) job_base[i + 1] = job_base[i] + job_counts[i];
     }
-    const uint32_t M = scheme == 6 ? job_base[n] : (uint32_t)(jobs_per * n), Mw = M ? M : 1;
+    const uint32_t M = consistency ? job_base[n] : (uint32_t)(jobs_per * n), Mw = M ? M : 1;
     const DevLayout& D = pick_layout(S.set, Mw);
     hipStream_t st = dev().stream;
     // workspace
@@ -57,7 +59,7 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
         HIP_TRY(hipMalloc(&S.buf, off)); S.cap = off;
     }
     uint8_t* base = (uint8_t*)S.buf;
-    if (scheme == 6) HIP_TRY(hipMemcpyAsync(base + o_jb, job_base.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
+    if (consistency) HIP_TRY(hipMemcpyAsync(base + o_jb, job_base.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));
     const uint16_t tcb[2] = {0, (uint16_t)(D.nchunks + VP_NUM)};       // one target: the fixed chunks and the 17 proof-point products
     HIP_TRY(hipMemcpyAsync(base + o_tcb, tcb, sizeof tcb, hipMemcpyHostToDevice, st));
@@ -66,8 +68,8 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
     V.bad = (int32_t*)(base + o_bad); V.pts = (uint32_t*)(base + o_pts); V.scal = (uint32_t*)(base + o_scal); V.digits = (uint32_t*)(base + o_dig);
     V.vscal = (uint32_t*)(base + o_vs); V.partial = (uint32_t*)(base + o_part); V.var_chunk0 = D.nchunks; V.table = dev().d_edg_table; V.wbits = dev().edg.wbits;
     V.job_base = (const uint32_t*)(base + o_jb); V.env_bad = (int32_t*)(base + o_eb);
-    if (scheme == 1) bpv_launch_parse(V, (uint32_t)n, stride, d_lens, d_mins, d_maxs, st);
-    else if (scheme == 3) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_lens, d_mins, st);
+    if (scheme == ZKP_HIP_OP_RANGE) bpv_launch_parse(V, (uint32_t)n, stride, d_lens, d_mins, d_maxs, st);
+    else if (scheme == ZKP_HIP_OP_THRESHOLD) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_lens, d_mins, st);
     else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_lens, st);
     uint32_t* enc = (uint32_t*)(base + o_enc);
     bool accepted_as_a_batch = false;
@@ -125,7 +127,7 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
         launch_sum_ed(R, sums, st);
         k_encode<<<dim3((M + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
     }
-    if (scheme == 6) bpv_launch_final_ranges(V, enc, (uint32_t)n, d_ok, st);
+    if (consistency) bpv_launch_final_ranges(V, enc, (uint32_t)n, d_ok, st);
     else bpv_launch_final(V, enc, (uint32_t)n, d_ok, jobs_per, st);
     HIP_TRY(hipGetLastError());
     if (ok_host) HIP_TRY(hipMemcpyAsync(ok_host, d_ok, n, hipMemcpyDeviceToHost, st));
@@ -140,35 +142,28 @@ std::vector<uint32_t> consistency_job_counts(uint64_t n, const uint8_t* proofs, 
     for (uint64_t i = 0; i < n; i++) job_counts[i] = lens[i] <= stride ? ve_consistency_jobs(proofs + stride * i, lens[i]) : 0u;
     return job_counts;
 }
-// the host-buffer entry points: upload, then the core above (the consistency job counts are read from the envelopes' own k fields)
-int verify_bp_locked(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
-    std::vector<uint32_t> job_counts;
-    if (scheme == 6) job_counts = consistency_job_counts(n, proofs, stride, lens);
-    hipStream_t st = dev().stream;
-    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t *d_min = nullptr, *d_max = nullptr;
-    DevScope mem;
-    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_len, 4 * n)); HIP_TRY(mem.alloc(&d_ok, n));
-    if (mins) HIP_TRY(mem.alloc(&d_min, 8 * n));
-    if (maxs) HIP_TRY(mem.alloc(&d_max, 8 * n));
-    HIP_TRY(hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st));
-    if (mins) HIP_TRY(hipMemcpyAsync(d_min, mins, 8 * n, hipMemcpyHostToDevice, st));
-    if (maxs) HIP_TRY(hipMemcpyAsync(d_max, maxs, 8 * n, hipMemcpyHostToDevice, st));
-    return verify_bp_device(scheme, n, d_in, stride, d_len, d_min, d_max, d_ok, job_counts.data(), ok);
-}
+// the batch-check threshold in force (ZKP_HIP_BATCH_VERIFY_MIN, read on every call) as the minimum slice of a fanned-out call
+uint64_t bp_min_slice() { const int v = env_int("ZKP_HIP_BATCH_VERIFY_MIN", (int)RLC_MIN_JOBS); return v > 0 ? (uint64_t)v : RLC_MIN_JOBS; }
 
-// The same over every registered shard when the plan of verify_shards.h says so (*fanned), one slice per shard through verify_bp_locked: every
-// slice draws its own weights and makes its own batch check.  Minimum slice: the batch-check threshold in force (ZKP_HIP_BATCH_VERIFY_MIN).
-int verify_bp_fanned(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok, bool* fanned) {
-    *fanned = false;
-    const std::vector<Device*> shards = verify_fanout_candidates();
-    if (shards.empty()) return 0;
-    std::vector<uint64_t> prefix;
-    if (scheme == 6) { prefix.resize(n + 1); vs_prefix(n, consistency_job_counts(n, proofs, stride, lens).data(), prefix.data()); }
-    const int rlc_min = env_int("ZKP_HIP_BATCH_VERIFY_MIN", (int)RLC_MIN_JOBS);
-    return verify_fan_out(shards, nullptr, n, scheme == 6 ? prefix.data() : nullptr, scheme == 1 ? 2u : 1u, rlc_min > 0 ? (uint64_t)rlc_min : RLC_MIN_JOBS,
-                          [&](uint64_t lo, uint64_t m) { return verify_bp_locked(scheme, m, proofs + stride * lo, stride, lens + lo, mins ? mins + lo : nullptr, maxs ? maxs + lo : nullptr, ok + lo); },
-                          fanned);
+// one slice of a host-buffer call on the bound shard: the consistency job counts from the envelopes' own k fields, the upload, the core above
+int verify_bp_host(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
+    std::vector<uint32_t> job_counts;
+    if (scheme == ZKP_HIP_OP_CONSISTENCY) job_counts = consistency_job_counts(n, proofs, stride, lens);
+    EnvelopeUpload up;
+    int rc = up.open(n, proofs, stride, lens, mins, maxs);
+    if (rc) return rc;
+    return verify_bp_device(scheme, n, up.d_in, stride, up.d_len, up.d_p0, up.d_p1, up.d_ok, job_counts.data(), ok);
+}
+// The three host-buffer entry points after their argument checks.  Spread over the shards (verify_call), every slice draws its own weights
+// and makes its own batch check.  Weights: two jobs per range envelope, one per threshold envelope, a consistency envelope's own job count.
+int verify_bp_call(int scheme, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) {
+    return verify_call(n,
+        [&](const std::vector<Device*>&, VerifyFanout& F) {
+            if (scheme == ZKP_HIP_OP_CONSISTENCY) { F.prefix.resize(n + 1); vs_prefix(n, consistency_job_counts(n, proofs, stride, lens).data(), F.prefix.data()); }
+            F.unit = scheme == ZKP_HIP_OP_RANGE ? 2u : 1u; F.min_jobs = bp_min_slice();
+            return 0;
+        },
+        [&](uint64_t lo, uint64_t m) { return verify_bp_host(scheme, m, proofs + stride * lo, stride, lens + lo, mins ? mins + lo : nullptr, maxs ? maxs + lo : nullptr, ok + lo); });
 }
 
 void bpv_release_all() {
@@ -184,38 +179,20 @@ extern "C" {
 
 int zkp_hip_verify_range_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* mins, const uint64_t* maxs, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, mins, maxs, ok}, stride);
-    if (rc) return rc;
-    bool fanned = false;
-    rc = verify_bp_fanned(1, n, proofs, stride, lens, mins, maxs, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_bp_locked(1, n, proofs, stride, lens, mins, maxs, ok);
+    const int rc = verifier_args(n, {proofs, lens, mins, maxs, ok}, stride);
+    return rc ? rc : verify_bp_call(ZKP_HIP_OP_RANGE, n, proofs, stride, lens, mins, maxs, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_threshold_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* thresholds, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, thresholds, ok}, stride);
-    if (rc) return rc;
-    bool fanned = false;
-    rc = verify_bp_fanned(3, n, proofs, stride, lens, thresholds, nullptr, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_bp_locked(3, n, proofs, stride, lens, thresholds, nullptr, ok);
+    const int rc = verifier_args(n, {proofs, lens, thresholds, ok}, stride);
+    return rc ? rc : verify_bp_call(ZKP_HIP_OP_THRESHOLD, n, proofs, stride, lens, thresholds, nullptr, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_consistency_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc) return rc;
-    bool fanned = false;
-    rc = verify_bp_fanned(6, n, proofs, stride, lens, nullptr, nullptr, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_bp_locked(6, n, proofs, stride, lens, nullptr, nullptr, ok);
+    const int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    return rc ? rc : verify_bp_call(ZKP_HIP_OP_CONSISTENCY, n, proofs, stride, lens, nullptr, nullptr, ok);
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // Groth16 / BN254 host side of libzkp_hip (included by zkp_hip.hip): R1CS of libzkp's two circuits, ark-serialize
-// proving-key loader, fixed-base table construction and the batched prove pipeline.  Kernels: g16_kernels.hip.
+// proving-key loader, fixed-base table construction, the batched prove pipeline, and the verifier: its core on device pointers
+// (verify_g16_core), one slice of a host-buffer call (verify_g16_host) and the two entry points on verify_call.  Kernels: g16_kernels.hip,
+// g16_verify_kernels.hip, fq2vm_kernels.hip.
 
 // ================================================================================================ host
 namespace {
@@ -151,7 +153,7 @@ uint64_t key_table_bytes(size_t n1, size_t n2, uint32_t wbits, bool uneven = fal
     const G16Radix rx = g16_radix(wbits, uneven);
     return ((uint64_t)n1 * g16_table_entry_words(false, true) + (uint64_t)n2 * g16_table_entry_words(true, true)) * 4ull * rx.slot_ent;
 }
-// The radix of a key's tables.  DEFAULT: 2^13 (19-20 windows of 4096 entries: ~34 GB for the two circuits of libzkp together) -- the knee
+// The radix of a key's tables.  DEFAULT: 2^13 (19-20 windows of 4096 entries: 27.8 GB measured for the two circuits of libzkp together) -- the knee
 // of the measured curve (DESIGN.md 6b: 2^14-uneven, ~72 GB, is 1.7 % faster on the mixed batch; 2^13 against even 2^14: 0.4 %), because a
 // drop-in library should not take a quarter of a 288 GB device silently.  Opt-ins: ZKP_HIP_G16_TABLE_BUDGET_MB=<MB per key> takes the
 // largest radix (2^14 in its uneven form first) whose tables fit that budget; ZKP_HIP_G16_WBITS=8..15 forces one.  In every case the
@@ -605,26 +607,26 @@ void g16_release_all() {
 // The per-envelope check of n envelopes that lie in device memory, verdicts into d_ok (and into ok, host memory, when it is given); waits for
 // them.  The Fq2 machine (fq2vm.h) checks every envelope whose proof points are all finite; a batch that holds any other valid encoding (a
 // point at infinity drops a pair from the product) goes through the lane-per-chain kernels as a whole, which handle those cases; use_vm = false
-// takes the lane-per-chain kernels for everything.  `e`: the state of the caller's earlier asynchronous calls on the stream.
-int verify_g16_device(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, uint8_t* d_ok, uint8_t* ok, bool use_vm, DevScope& mem, hipError_t e) {
+// takes the lane-per-chain kernels for everything.  `mem` owns the scratch; the caller holds a Quiesce behind it (zkp_hip.hip).
+int verify_g16_device(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, uint8_t* d_ok, uint8_t* ok, bool use_vm, DevScope& mem) {
     hipStream_t st = dev().stream;
     if (use_vm) {
         uint8_t* d_scratch = nullptr; uint32_t* d_special = nullptr; uint32_t special = 0;
         HIP_TRY(mem.alloc(&d_scratch, g16_vm_scratch_bytes(n))); HIP_TRY(mem.alloc(&d_special, 4));
-        if (e == hipSuccess) e = hipMemsetAsync(d_special, 0, 4, st);
-        if (e == hipSuccess) { g16_launch_verify_vm(kind, d_in, stride, d_len, n, K.vk, g16s().vm, K.vm_kconst, K.vm_lines, d_scratch, d_ok, d_special, st); e = hipGetLastError(); }
-        if (e == hipSuccess && ok) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&special, d_special, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(d_special, 0, 4, st));
+        g16_launch_verify_vm(kind, d_in, stride, d_len, n, K.vk, g16s().vm, K.vm_kconst, K.vm_lines, d_scratch, d_ok, d_special, st);
+        HIP_TRY(hipGetLastError());
+        if (ok) HIP_TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&special, d_special, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (!special) return 0;          // (the stream synchronisation above came after the chains' join)
     }
     uint8_t* d_scratch2 = nullptr;
     HIP_TRY(mem.alloc(&d_scratch2, g16_verify_scratch_bytes(n)));
-    if (e == hipSuccess) { g16_launch_verify(kind, d_in, stride, d_len, n, K.vk, d_scratch2, d_ok, st); e = hipGetLastError(); }
-    if (e == hipSuccess && ok) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+    g16_launch_verify(kind, d_in, stride, d_len, n, K.vk, d_scratch2, d_ok, st);
+    HIP_TRY(hipGetLastError());
+    if (ok) HIP_TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -635,8 +637,9 @@ struct G16VerifyTally {
     uint64_t segment_checks = 0, envelopes = 0;
     explicit G16VerifyTally(Device& dv) : d(dv) {}
     ~G16VerifyTally() {
-        d.g16_verify.launches += segment_checks; d.g16_verify.adds += envelopes;
-        d.g16_verify.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        Device::HostCounter& C = d.counter(ZKP_HIP_COUNTER_G16_VERIFY);
+        C.a += segment_checks; C.b += envelopes;
+        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 };
 
@@ -673,7 +676,7 @@ int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, cons
     g16_launch_compact(d_in, stride, d_len, n, g, d_loc, d_off, d_in2, d_len2, st);
     HIP_TRY(hipGetLastError());
     tally.envelopes += m;
-    int rc = verify_g16_device(kind, K, d_in2, stride, d_len2, m, d_ok2, nullptr, true, mem, hipSuccess);
+    int rc = verify_g16_device(kind, K, d_in2, stride, d_len2, m, d_ok2, nullptr, true, mem);
     if (rc) return rc;
     g16_launch_scatter(n, g, d_loc, d_off, d_ok2, d_ok, st);
     HIP_TRY(hipGetLastError());
@@ -688,10 +691,9 @@ int g16_rlc_min() { static const int v = env_int("ZKP_HIP_G16_BATCH_VERIFY_MIN",
 // Verdicts of n envelopes that lie in device memory (d_in, `stride` bytes each, d_len[i] bytes used) into d_ok (device) and ok (host, n bytes:
 // the localisation pass reads the batch check's verdicts there): one weighted pairing check for a large batch (g16_rlc.h); when it does not
 // stand, the localisation pass and the per-envelope check of the suspect envelopes, or of all of them.  ZKP_HIP_G16_VERIFY_VM=0 (tuning / test
-// knob) takes the lane-per-chain kernels for everything.  `mem` owns the scratch and `e` is the state of the caller's earlier asynchronous calls
-// on the shard's stream.  The chains run on side streams against that scratch: after a failure (a non-zero return) the caller waits for the
-// whole device before `mem` hands its blocks back (Quiesce in verify_g16_host).
-int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint8_t* d_ok, uint8_t* ok, DevScope& mem, hipError_t e) {
+// knob) takes the lane-per-chain kernels for everything.  `mem` owns the scratch.  The chains run on side streams against that scratch: after
+// a failure (a non-zero return) the caller waits for the whole device before `mem` hands its blocks back (Quiesce, zkp_hip.hip).
+int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint8_t* d_ok, uint8_t* ok, DevScope& mem) {
     G16Key& K = g16s().key[kind];
     if (!K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
     hipStream_t st = dev().stream;
@@ -716,13 +718,13 @@ int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, 
             std::vector<uint8_t> rnd; { int rcs = fresh_seeds(rnd, (n + 1) / 2); if (rcs) return rcs; }          // 16 bytes per envelope
             for (uint64_t j = 0; j < n; j++) { bool z = true; for (int k = 0; k < 16; k++) z = z && rnd[16 * j + k] == 0; if (z) rnd[16 * j] = 1; }
             uint32_t counters[4] = {0, 0, 0, 0};
-            if (e == hipSuccess) e = hipMemcpyAsync(d_rlc + g16_rlc_rho_offset((uint32_t)n, n_ic), rnd.data(), 16 * n, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemsetAsync(d_rlc + g16_rlc_counters_offset((uint32_t)n, n_ic), 0, sizeof counters, st);
-            if (e == hipSuccess) { g16_launch_verify_rlc(kind, d_in, stride, d_len, (uint32_t)n, K.vk, T, K.vm_kconst, K.vm_lines, d_rlc, d_ok, st); e = hipGetLastError(); }
-            if (e == hipSuccess) e = hipMemcpyAsync(counters, d_rlc + g16_rlc_counters_offset((uint32_t)n, n_ic), sizeof counters, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+            HIP_TRY(hipMemcpyAsync(d_rlc + g16_rlc_rho_offset((uint32_t)n, n_ic), rnd.data(), 16 * n, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_rlc + g16_rlc_counters_offset((uint32_t)n, n_ic), 0, sizeof counters, st));
+            g16_launch_verify_rlc(kind, d_in, stride, d_len, (uint32_t)n, K.vk, T, K.vm_kconst, K.vm_lines, d_rlc, d_ok, st);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(counters, d_rlc + g16_rlc_counters_offset((uint32_t)n, n_ic), sizeof counters, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             if (counters[0] == 0 && counters[1] == 0 && counters[2] == 0 && counters[3] == 1) return 0;
             if (getenv("ZKP_HIP_G16_BATCH_VERIFY_ONLY")) {          // diagnostic (tests): say that the batch check did not stand instead of verifying again
                 char msg[160]; snprintf(msg, sizeof msg, "the batch check did not stand (special %u, outside the subgroup %u, anomalies %u, product is one: %u)", counters[0], counters[1], counters[2], counters[3]);
@@ -736,39 +738,34 @@ int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, 
             tally->envelopes += n;
         }
     }
-    return verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem, e);
+    return verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem);
 }
 
-// the host-buffer entry points: upload, then the core above
+// the batch-check threshold in force (ZKP_HIP_G16_BATCH_VERIFY_MIN) as the minimum slice of a fanned-out call
+uint64_t g16_min_slice() { const int v = g16_rlc_min(); return v > 0 ? (uint64_t)v : 8193u; }
+bool g16_shard_holds_vk(Device* d, int kind) { std::lock_guard<std::mutex> lk(d->mu); return d->g16 && d->g16->key[kind].vk_ready; }
+
+// one slice of a host-buffer call on the bound shard: upload, then the core above
 int verify_g16_host(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
     if (!g16s().key[kind].vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
-    hipStream_t st = dev().stream;
-    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr;
-    DevScope mem;
-    // Chain B and the subgroup chain of the Fq2 machine run on the tables' side streams against d_scratch; DevScope only quiesces the
-    // shard's main stream, so every early return below first waits for the whole device before the blocks go back to the pool.
-    struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;
-    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_ok, n)); HIP_TRY(mem.alloc(&d_len, 4 * n));
-    hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
-    const int rc = verify_g16_core(kind, n, d_in, stride, d_len, d_ok, ok, mem, e);
-    if (rc) return rc;
+    EnvelopeUpload up;
+    Quiesce quiesce;
+    int rc = up.open(n, proofs, stride, lens);
+    if (rc || (rc = verify_g16_core(kind, n, up.d_in, stride, up.d_len, up.d_ok, ok, up.mem))) return rc;
     quiesce.armed = false;
     return 0;
 }
-
-// The same over the registered shards that hold a usable key of `kind` when the plan of verify_shards.h says so (*fanned), one slice per
-// shard through verify_g16_host: every slice draws its own weights and makes its own batch check.  A caller's shard without the key: not
-// fanned, and the usual path reports the missing key.  Minimum slice: the batch-check threshold in force (ZKP_HIP_G16_BATCH_VERIFY_MIN).
-int verify_g16_fanned(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok, bool* fanned) {
-    *fanned = false;
-    const std::vector<Device*> shards = verify_fanout_candidates();
-    if (shards.empty()) return 0;
-    std::vector<uint8_t> holds(shards.size());
-    for (size_t k = 0; k < shards.size(); k++) { std::lock_guard<std::mutex> lk(shards[k]->mu); holds[k] = shards[k]->g16 && shards[k]->g16->key[kind].vk_ready; }
-    const int rlc_min = g16_rlc_min();
-    return verify_fan_out(shards, holds.data(), n, nullptr, 1u, rlc_min > 0 ? (uint64_t)rlc_min : 8193u,
-                          [&](uint64_t lo, uint64_t m) { return verify_g16_host(kind, m, proofs + stride * lo, stride, lens + lo, ok + lo); }, fanned);
+// The two host-buffer entry points after their argument checks.  Spread over the registered shards that hold a usable key of `kind`
+// (verify_call), every slice draws its own weights and makes its own batch check.  A caller's shard without the key: not fanned, and the usual
+// path reports the missing key.
+int verify_g16_call(int kind, uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) {
+    return verify_call(n,
+        [&](const std::vector<Device*>& shards, VerifyFanout& F) {
+            for (Device* d : shards) F.holds.push_back(g16_shard_holds_vk(d, kind));
+            F.min_jobs = g16_min_slice();
+            return 0;
+        },
+        [&](uint64_t lo, uint64_t m) { return verify_g16_host(kind, m, proofs + stride * lo, stride, lens + lo, ok + lo); });
 }
 
 }  // namespace
@@ -839,25 +836,13 @@ int zkp_hip_groth16_generate_key(int kind, const uint8_t* setup_seed, uint8_t* p
 
 int zkp_hip_verify_equality_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc) return rc;
-    bool fanned = false;
-    rc = verify_g16_fanned(G16_EQUALITY, n, proofs, stride, lens, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_g16_host(G16_EQUALITY, n, proofs, stride, lens, ok);
+    const int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    return rc ? rc : verify_g16_call(G16_EQUALITY, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 int zkp_hip_verify_membership_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, ok}, stride);
-    if (rc) return rc;
-    bool fanned = false;
-    rc = verify_g16_fanned(G16_MEMBERSHIP, n, proofs, stride, lens, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_g16_host(G16_MEMBERSHIP, n, proofs, stride, lens, ok);
+    const int rc = verifier_args(n, {proofs, lens, ok}, stride);
+    return rc ? rc : verify_g16_call(G16_MEMBERSHIP, n, proofs, stride, lens, ok);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_snark_commit_value_batch(uint64_t n, const uint64_t* values, uint8_t* out) try {

@@ -1,4 +1,5 @@
-// Improvement proofs (STARK) host side of libzkp_hip (included by zkp_hip.hip).  Kernel: stark_kernels.hip.
+// Improvement proofs (STARK) host side of libzkp_hip (included by zkp_hip.hip): the constants, the provers, the verifier's core on device
+// pointers (verify_stark_device), one slice of a host-buffer call (verify_stark_host) and its entry point on verify_call.  Kernel: stark_kernels.hip.
 namespace {
 
 struct StarkState { StarkConst* consts = nullptr; };       // per shard (Device::stark)
@@ -27,40 +28,28 @@ int verify_stark_device(uint64_t n, const uint8_t* d_in, uint64_t stride, const 
     return 0;
 }
 
-// the host-buffer entry point on the bound shard: upload, the core above, verdicts back
+// one slice of a host-buffer call on the bound shard: upload, the core above, verdicts back
 int verify_stark_host(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* old_values, uint8_t* ok) {
     int rc = ensure_stark_constants();
     if (rc) return rc;
-    hipStream_t st = dev().stream;
-    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t* d_old = nullptr;
-    DevScope mem;
-    HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_ok, n)); HIP_TRY(mem.alloc(&d_len, 4 * n)); HIP_TRY(mem.alloc(&d_old, 8 * n));
-    hipError_t e = hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_old, old_values, 8 * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && (rc = verify_stark_device(n, d_in, stride, d_len, d_old, d_ok))) return rc;
-    if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(ZKP_HIP_E_RUNTIME, hipGetErrorString(e));
+    EnvelopeUpload up;
+    if ((rc = up.open(n, proofs, stride, lens, old_values)) || (rc = verify_stark_device(n, up.d_in, stride, up.d_len, up.d_p0, up.d_ok))) return rc;
+    HIP_TRY(hipMemcpyAsync(ok, up.d_ok, n, hipMemcpyDeviceToHost, dev().stream));
+    HIP_TRY(hipStreamSynchronize(dev().stream));
     return 0;
 }
-// The same over every registered shard when the plan of verify_shards.h says so (*fanned).  The STARK verifier has no batch check; its
-// minimum slice is what fills a GPU -- the envelopes (one per lane, 64 per workgroup) of the k_stark_verify workgroups the caller's GPU holds
-// at once, asked once per shard under a short Bind of its own that is gone before anything is posted: a slice that does not fill a GPU
-// cannot finish sooner on two.  An occupancy query that fails keeps the call on the caller's shard.
-int verify_stark_fanned(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* old_values, uint8_t* ok, bool* fanned) {
-    *fanned = false;
-    const std::vector<Device*> shards = verify_fanout_candidates();
-    if (shards.empty()) return 0;
-    uint64_t resident = 0;
-    if (env_int("ZKP_HIP_VERIFY_SHARD_MIN", 0) <= 0) {
-        Bind bind; int rc = bind.open();
-        if (rc) return rc;
-        if (!dev().stark_verify_resident) dev().stark_verify_resident = (uint64_t)stark_verify_blocks_per_cu() * (uint64_t)dev().num_cu * 64u;
-        if (!(resident = dev().stark_verify_resident)) return 0;
-    }
-    return verify_fan_out(shards, nullptr, n, nullptr, 1u, resident,
-                          [&](uint64_t lo, uint64_t m) { return verify_stark_host(m, proofs + stride * lo, stride, lens + lo, old_values + lo, ok + lo); }, fanned);
+// The minimum slice of a fanned-out call.  The STARK verifier has no batch check; what it needs is what fills a GPU -- the envelopes (one per
+// lane, 64 per workgroup) of the k_stark_verify workgroups the caller's GPU holds at once, asked once per shard under a short Bind of its own
+// that is gone before anything is posted: a slice that does not fill a GPU cannot finish sooner on two.  An occupancy query that fails keeps
+// the call on the caller's shard (no slice is large enough).  Not asked when ZKP_HIP_VERIFY_SHARD_MIN replaces the minimum anyway.
+int stark_min_slice(uint64_t* min_jobs) {
+    *min_jobs = 0;
+    if (env_int("ZKP_HIP_VERIFY_SHARD_MIN", 0) > 0) return 0;
+    Bind bind; int rc = bind.open();
+    if (rc) return rc;
+    if (!dev().stark_verify_resident) dev().stark_verify_resident = (uint64_t)stark_verify_blocks_per_cu() * (uint64_t)dev().num_cu * 64u;
+    *min_jobs = dev().stark_verify_resident ? dev().stark_verify_resident : ~0ull;
+    return 0;
 }
 
 void stark_release_all() {
@@ -117,14 +106,10 @@ int zkp_hip_prove_improvement_batch(uint64_t n, const uint64_t* old_values, cons
 
 int zkp_hip_verify_improvement_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* old_values, uint8_t* ok) try {
     if (n == 0) return 0;
-    int rc = verifier_args(n, {proofs, lens, old_values, ok}, stride);
+    const int rc = verifier_args(n, {proofs, lens, old_values, ok}, stride);
     if (rc) return rc;
-    bool fanned = false;
-    rc = verify_stark_fanned(n, proofs, stride, lens, old_values, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_stark_host(n, proofs, stride, lens, old_values, ok);
+    return verify_call(n, [&](const std::vector<Device*>&, VerifyFanout& F) { return stark_min_slice(&F.min_jobs); },
+                       [&](uint64_t lo, uint64_t m) { return verify_stark_host(m, proofs + stride * lo, stride, lens + lo, old_values + lo, ok + lo); });
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

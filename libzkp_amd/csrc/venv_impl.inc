@@ -1,6 +1,6 @@
 // The mixed verifier (include/libzkp_hip_verify.h), host side and glue kernels of libzkp_hip (included by zkp_hip.hip).  Steps: venv_steps.h.
 // The verifiers themselves are the cores of the per-scheme calls (verify_bp_device, verify_g16_core, verify_stark_device), called unchanged,
-// one after the other on the shard's stream in self_check_shard's order.
+// one after the other on the shard's stream by verify_scheme_passes below, which the batch self-check (batch_impl.inc) runs too.
 static_assert(VE_RANGE_PROOF_BYTES == RP_BYTES, "venv_steps.h: the range proof inside a consistency envelope");
 static_assert(SC_KINDS == ZKP_HIP_OP_CONSISTENCY + 1, "scheme bytes index the row plan");
 
@@ -20,13 +20,44 @@ __global__ void __launch_bounds__(256) k_venv_apply(VenvView V, uint8_t* ok) {
 
 namespace {
 
+// One scheme's rows for verify_scheme_passes: n envelopes at `stride` bytes in `rows`, lens[i] bytes used, verdicts into ok (all device
+// pointers); p0 / p1: the scheme's parameter columns (range: mins, maxs; threshold: thresholds; improvement: old values); jobs: a consistency
+// envelope's job counts (host, n entries).
+struct SchemePass { uint64_t n = 0; const uint8_t* rows = nullptr; uint64_t stride = 0; const uint32_t* lens = nullptr; const uint64_t *p0 = nullptr, *p1 = nullptr;
+                    uint8_t* ok = nullptr; const uint32_t* jobs = nullptr; };
+// Each scheme's verifier core over its rows (K is indexed by ZKP_HIP_OP_*), one after the other on the bound shard's stream: range, threshold,
+// consistency, equality, membership, improvement; a kind without rows is skipped.  *passes (may be null) is raised by the number run.  The two
+// Groth16 kinds share one host copy of the batch check's verdicts and run under a Quiesce: their scratch comes from the caller's `mem`.
+// after_g16() runs behind them when either had rows (the self-check binds their public inputs there).
+template <class F> int verify_scheme_passes(const SchemePass (&K)[SC_KINDS], DevScope& mem, uint64_t* passes, F after_g16) {
+    int rc;
+    uint64_t ran = 0;
+    for (int s : {ZKP_HIP_OP_RANGE, ZKP_HIP_OP_THRESHOLD, ZKP_HIP_OP_CONSISTENCY}) {
+        const SchemePass& k = K[s];
+        if (!k.n) continue;
+        ran++;
+        if ((rc = verify_bp_device(s, k.n, k.rows, k.stride, k.lens, k.p0, k.p1, k.ok, k.jobs, nullptr))) return rc;
+    }
+    const SchemePass &eq = K[ZKP_HIP_OP_EQUALITY], &me = K[ZKP_HIP_OP_MEMBERSHIP], &im = K[ZKP_HIP_OP_IMPROVEMENT];
+    if (eq.n || me.n) {
+        Quiesce quiesce;
+        std::vector<uint8_t> h_ok(eq.n > me.n ? eq.n : me.n);      // the batch check's verdicts, read by its localisation pass
+        if (eq.n) { ran++; if ((rc = verify_g16_core(G16_EQUALITY, eq.n, eq.rows, eq.stride, eq.lens, eq.ok, h_ok.data(), mem))) return rc; }
+        if (me.n) { ran++; if ((rc = verify_g16_core(G16_MEMBERSHIP, me.n, me.rows, me.stride, me.lens, me.ok, h_ok.data(), mem))) return rc; }
+        quiesce.armed = false;
+        if ((rc = after_g16())) return rc;
+    }
+    if (im.n) { ran++; if ((rc = verify_stark_device(im.n, im.rows, im.stride, im.lens, im.p0, im.ok))) return rc; }
+    if (passes) *passes += ran;
+    return 0;
+}
+
 // The call on device pointers, on the bound shard: classification, the records back, the plan, the rows, the cores, the verdicts into d_ok
 // (device, n bytes); ok_host (may be null) also receives them before the wait that ends the call.
 int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const uint8_t* d_expect, uint8_t* d_ok, uint8_t* ok_host) {
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = dev().stream;
     DevScope mem;
-    struct Quiesce { bool armed = false; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } } quiesce;      // as verify_g16_host: the chains' side streams
     VenvRecord* d_rec = nullptr;
     HIP_TRY(mem.alloc(&d_rec, sizeof(VenvRecord) * n));
     const uint32_t lane_blocks = (uint32_t)((n + 255) / 256);
@@ -59,35 +90,20 @@ int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_o
         HIP_TRY(hipMemsetAsync(V.row_ok, 0, R, st));
         k_venv_unpack<<<(uint32_t)((n + VENV_UNPACK_TB / 64 - 1) / (VENV_UNPACK_TB / 64)), VENV_UNPACK_TB, 0, st>>>(V);
         HIP_TRY(hipGetLastError());
-        int rc;
-        auto rows_of = [&](uint32_t k) { return (const uint8_t*)(V.rows + P.base[k]); };
-        auto lens = [&](uint32_t k) { return (const uint32_t*)(V.row_len + P.row0[k]); };
-        auto p0 = [&](uint32_t k) { return (const uint64_t*)(V.row_p0 + P.row0[k]); };
-        auto oks = [&](uint32_t k) { return V.row_ok + P.row0[k]; };
-        const uint32_t RG = ZKP_HIP_OP_RANGE, TH = ZKP_HIP_OP_THRESHOLD, CO = ZKP_HIP_OP_CONSISTENCY, EQ = ZKP_HIP_OP_EQUALITY, ME = ZKP_HIP_OP_MEMBERSHIP, IM = ZKP_HIP_OP_IMPROVEMENT;
-        if (P.rows[RG]) { passes++; if ((rc = verify_bp_device(1, P.rows[RG], rows_of(RG), P.stride[RG], lens(RG), p0(RG), V.row_p1 + P.row0[RG], oks(RG), nullptr, nullptr))) return rc; }
-        if (P.rows[TH]) { passes++; if ((rc = verify_bp_device(3, P.rows[TH], rows_of(TH), P.stride[TH], lens(TH), p0(TH), nullptr, oks(TH), nullptr, nullptr))) return rc; }
-        if (P.rows[CO]) {
-            std::vector<uint32_t> jobs; jobs.reserve(P.rows[CO]);          // in row order = envelope order
-            for (uint64_t i = 0; i < n; i++) if (rec[i].scheme == CO) jobs.push_back(rec[i].jobs);
-            passes++;
-            if ((rc = verify_bp_device(6, P.rows[CO], rows_of(CO), P.stride[CO], lens(CO), nullptr, nullptr, oks(CO), jobs.data(), nullptr))) return rc;
-        }
-        if (P.rows[EQ] || P.rows[ME]) {
-            quiesce.armed = true;
-            std::vector<uint8_t> h_ok(P.rows[EQ] > P.rows[ME] ? P.rows[EQ] : P.rows[ME]);      // the batch check's verdicts, read by its localisation pass
-            if (P.rows[EQ]) { passes++; if ((rc = verify_g16_core(G16_EQUALITY, P.rows[EQ], rows_of(EQ), P.stride[EQ], lens(EQ), oks(EQ), h_ok.data(), mem, hipSuccess))) return rc; }
-            if (P.rows[ME]) { passes++; if ((rc = verify_g16_core(G16_MEMBERSHIP, P.rows[ME], rows_of(ME), P.stride[ME], lens(ME), oks(ME), h_ok.data(), mem, hipSuccess))) return rc; }
-            quiesce.armed = false;
-        }
-        if (P.rows[IM]) { passes++; if ((rc = verify_stark_device(P.rows[IM], rows_of(IM), P.stride[IM], lens(IM), p0(IM), oks(IM)))) return rc; }
+        std::vector<uint32_t> jobs; jobs.reserve(P.rows[ZKP_HIP_OP_CONSISTENCY]);          // in row order = envelope order
+        if (P.rows[ZKP_HIP_OP_CONSISTENCY]) for (uint64_t i = 0; i < n; i++) if (rec[i].scheme == ZKP_HIP_OP_CONSISTENCY) jobs.push_back(rec[i].jobs);
+        SchemePass K[SC_KINDS];          // (a core ignores the columns its scheme has no use for)
+        for (uint32_t k = 0; k < SC_KINDS; k++)
+            K[k] = {P.rows[k], V.rows + P.base[k], P.stride[k], V.row_len + P.row0[k], V.row_p0 + P.row0[k], V.row_p1 + P.row0[k], V.row_ok + P.row0[k], jobs.data()};
+        const int rc = verify_scheme_passes(K, mem, &passes, [] { return 0; });
+        if (rc) return rc;
     }
     k_venv_apply<<<lane_blocks, 256, 0, st>>>(V, d_ok);
     HIP_TRY(hipGetLastError());
     if (ok_host) HIP_TRY(hipMemcpyAsync(ok_host, d_ok, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    Device::VerifyMixedStats& C = dev().verify_mixed;
-    C.passes += passes; C.rows += P.live;
+    Device::HostCounter& C = dev().counter(ZKP_HIP_COUNTER_VERIFY_MIXED);
+    C.a += passes; C.b += P.live;
     C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
@@ -111,13 +127,9 @@ int verify_envelopes_host(uint64_t m, const uint8_t* blob, const uint64_t* off, 
     return verify_envelopes_core(m, d_blob, d_off, d_expect, d_ok, ok);
 }
 
-// The host-buffer form over every registered shard when the plan of verify_shards.h says so (*fanned): contiguous slices through
-// verify_envelopes_host.  Weights: ve_weight.  Minimum slice: the larger of the two batch-check thresholds in force.  Shards that lack a
-// usable key of a Groth16 circuit whose scheme byte occurs in the list take no part.
-int verify_envelopes_fanned(uint64_t n, const uint8_t* blob, const uint64_t* off, const uint8_t* expect, uint8_t* ok, bool* fanned) {
-    *fanned = false;
-    const std::vector<Device*> shards = verify_fanout_candidates();
-    if (shards.empty()) return 0;
+// The fan-out data of the host-buffer form (verify_call).  Weights: ve_weight.  Minimum slice: the larger of the two batch-check thresholds
+// in force.  Shards that lack a usable key of a Groth16 circuit whose scheme byte occurs in the list take no part.
+int verify_envelopes_plan(uint64_t n, const uint8_t* blob, const uint64_t* off, const std::vector<Device*>& shards, VerifyFanout& F) {
     std::vector<uint32_t> weights(n);
     bool need[2] = {false, false};
     for (uint64_t i = 0; i < n; i++) {
@@ -128,19 +140,15 @@ int verify_envelopes_fanned(uint64_t n, const uint8_t* blob, const uint64_t* off
             if (s == ZKP_HIP_OP_MEMBERSHIP) need[G16_MEMBERSHIP] = true;
         }
     }
-    std::vector<uint64_t> prefix(n + 1);
-    vs_prefix(n, weights.data(), prefix.data());
-    std::vector<uint8_t> holds(shards.size());
-    for (size_t k = 0; k < shards.size(); k++) {
-        std::lock_guard<std::mutex> lk(shards[k]->mu);
+    F.prefix.resize(n + 1);
+    vs_prefix(n, weights.data(), F.prefix.data());
+    for (Device* d : shards) {
         bool has = true;
-        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has = has && shards[k]->g16 && shards[k]->g16->key[kind].vk_ready;
-        holds[k] = has;
+        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has = has && g16_shard_holds_vk(d, kind);
+        F.holds.push_back(has);
     }
-    const int bp_min = env_int("ZKP_HIP_BATCH_VERIFY_MIN", (int)RLC_MIN_JOBS), g16_min = g16_rlc_min();
-    const uint64_t a = bp_min > 0 ? (uint64_t)bp_min : RLC_MIN_JOBS, b = g16_min > 0 ? (uint64_t)g16_min : 8193u;
-    return verify_fan_out(shards, holds.data(), n, prefix.data(), 0u, a > b ? a : b,
-                          [&](uint64_t lo, uint64_t m) { return verify_envelopes_host(m, blob, off + lo, expect ? expect + lo : nullptr, ok + lo); }, fanned);
+    F.unit = 0; F.min_jobs = std::max(bp_min_slice(), g16_min_slice());
+    return 0;
 }
 
 }  // namespace
@@ -153,12 +161,8 @@ int zkp_hip_verify_envelopes(uint64_t n, const uint8_t* blob, const uint64_t* of
     if (rc) return rc;
     if (!off || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     if (!blob && off[n] > off[0]) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    bool fanned = false;
-    rc = verify_envelopes_fanned(n, blob, off, expect, ok, &fanned);
-    if (rc || fanned) return rc;
-    Bind bind;
-    if ((rc = bind.open())) return rc;
-    return verify_envelopes_host(n, blob, off, expect, ok);
+    return verify_call(n, [&](const std::vector<Device*>& shards, VerifyFanout& F) { return verify_envelopes_plan(n, blob, off, shards, F); },
+                       [&](uint64_t lo, uint64_t m) { return verify_envelopes_host(m, blob, off + lo, expect ? expect + lo : nullptr, ok + lo); });
 } ZKP_API_CATCH_INT
 
 int zkp_hip_verify_envelopes_device(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const uint8_t* d_expect, uint8_t* d_ok) try {

@@ -1,12 +1,12 @@
 // How one zkp_hip_verify_*_batch call is cut over the registered shards: the planning, pure index arithmetic (no HIP calls, every sum in 64
-// bits) shared by the host (zkp_hip.hip: verify_fan_out and the six entry points) and the host build of tests/emul/emul_verify_shards.cpp.
+// bits) shared by the host (zkp_hip.hip: verify_call and verify_fan_out, under the seven host-buffer verify entry points) and the host build of tests/emul/emul_verify_shards.cpp.
 //
 // A call of n envelopes is cut into contiguous slices, in order, one per participating shard; every slice goes through the scheme's own
 // host-buffer verifier on its shard -- the same kernels, one set of launches per slice on that shard's stream.  EVERY SLICE DRAWS ITS OWN
 // FRESH WEIGHTS AND MAKES ITS OWN BATCH CHECK: soundness is per slice (2^-128 per slice instead of per call), nothing is combined across GPUs.
 //
 // Weights, in the jobs the verifiers count: a range envelope 2, a threshold / equality / membership / improvement envelope 1 (`unit`, with
-// prefix == nullptr), a consistency envelope the job count verify_bp_locked reads from its k field, counted as at least 1 so that a zero-job
+// prefix == nullptr), a consistency envelope the job count verify_bp_host reads from its k field, counted as at least 1 so that a zero-job
 // envelope still costs something (vs_prefix).
 // Slice count: min(shards, total / min_jobs, n), at least 1, lowered further until no slice is empty or lighter than min_jobs (an odd
 // min_jobs under weight 2, or one very heavy envelope, can leave a light slice at the first count): min_jobs is the scheme's batch-check

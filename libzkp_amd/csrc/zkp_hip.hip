@@ -274,6 +274,13 @@ struct DevScope {
         return e;
     }
 };
+// Waits for the WHOLE device when it goes out of scope armed.  The Groth16 verifier's Fq2 machine runs chain B and the subgroup chain on side
+// streams of its tables against scratch that the caller's DevScope owns, and a DevScope only waits for the shard's main stream: after a
+// non-zero return from a point where those chains may have been enqueued, the device must be idle before the scratch goes back to the pool.
+// Declare it AFTER the DevScope it protects (it is then destroyed first) and disarm it once verify_g16_core has returned 0 -- its last
+// stream synchronisation came after the chains' join.  Relied on by every caller of verify_g16_core: verify_g16_host (the equality /
+// membership entry points and their fanned-out slices) and verify_scheme_passes (the batch self-check and the mixed verifier).
+struct Quiesce { bool armed = true; ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); } };
 
 struct DevLayout {
     uint16_t *slot_base = nullptr, *chunk_begin = nullptr, *chunk_win0 = nullptr, *chunk_nwin = nullptr, *target_chunk_begin = nullptr;
@@ -336,14 +343,14 @@ struct Device {
         double ms = 0; uint64_t launches = 0, adds = 0;
     };
     KProf prof[3];                      // ZKP_HIP_KERNEL_MSM_ED25519 / _BN254_G1 / _BN254_G2
-    // ZKP_HIP_COUNTER_G16_VERIFY, always counted: what the Groth16 verifier did after batch checks that did not stand (g16_impl.inc: G16VerifyTally)
-    struct G16VerifyStats { double ms = 0; uint64_t launches = 0, adds = 0; } g16_verify;
-    // ZKP_HIP_COUNTER_BATCH_SELF_CHECK, always counted: ops verified / refused by the self-check of flagged batches, host ms from the end of proving (batch_impl.inc: self_check_shard)
-    struct SelfCheckStats { double ms = 0; uint64_t verified = 0, refused = 0; } self_check;
-    // ZKP_HIP_COUNTER_VERIFY_FANOUT, always counted: slices of fanned-out verify calls run on this shard and their envelopes; host ms of those calls on the caller's shard (verify_fan_out)
-    struct VerifyFanoutStats { double ms = 0; uint64_t slices = 0, envelopes = 0; } verify_fanout;
-    // ZKP_HIP_COUNTER_VERIFY_MIXED, always counted: scheme passes run by the mixed verifier on this shard, envelopes that got a row, host ms of its calls (venv_impl.inc)
-    struct VerifyMixedStats { double ms = 0; uint64_t passes = 0, rows = 0; } verify_mixed;
+    // The host-side counters of zkp_hip_profile_read_kernel, always counted: counter `which` is host[which - ZKP_HIP_COUNTER_G16_VERIFY] (counter()).
+    //   _G16_VERIFY        a: segment checks, b: envelopes verified one by one after batch checks that did not stand; ms: host time of those calls (G16VerifyTally)
+    //   _BATCH_SELF_CHECK  a: ops verified, b: ops refused by the self-check of flagged batches; ms: host time from the end of proving (self_check_shard)
+    //   _VERIFY_FANOUT     a: slices of fanned-out verify calls run on this shard, b: their envelopes; ms: host time of those calls, on the caller's shard (verify_fan_out)
+    //   _VERIFY_MIXED      a: scheme passes run by the mixed verifier on this shard, b: envelopes that got a row; ms: host time of its calls (verify_envelopes_core)
+    struct HostCounter { double ms = 0; uint64_t a = 0, b = 0; };
+    HostCounter host[ZKP_HIP_COUNTER_VERIFY_MIXED - ZKP_HIP_COUNTER_G16_VERIFY + 1];
+    HostCounter& counter(int which) { return host[which - ZKP_HIP_COUNTER_G16_VERIFY]; }
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -829,8 +836,8 @@ template <class F> int for_each_device(const std::vector<Device*>& devs, F f, bo
     return any;
 }
 
-// ---- One zkp_hip_verify_*_batch call over every registered shard (plan and rules: verify_shards.h).  The entry points call these after
-// argument validation and BEFORE any Bind: a thread that held its shard while posting to that shard's worker would wait for itself.
+// ---- One host-buffer verify call over every registered shard (plan and rules: verify_shards.h).  verify_call below is the body of the six
+// zkp_hip_verify_*_batch entry points and of zkp_hip_verify_envelopes after their argument checks.
 // The shards a call may spread over -- empty (the call stays on the caller's shard, as before) when one shard is registered, when
 // ZKP_HIP_VERIFY_SHARDS=0, or when this thread has selected a shard with zkp_hip_use_device: callers that run one host thread per GPU do
 // their own splitting and must not post to each other's shards.  Read on every call.
@@ -861,14 +868,51 @@ template <class F> int verify_fan_out(const std::vector<Device*>& shards, const 
     std::vector<Device*> devs(count);
     for (uint32_t k = 0; k < count; k++) devs[k] = shards[part[k]];
     const int rc = for_each_device(devs, [&](size_t k) {
-        Device::VerifyFanoutStats& T = dev().verify_fanout;
-        T.slices++; T.envelopes += bounds[k + 1] - bounds[k];
+        Device::HostCounter& T = dev().counter(ZKP_HIP_COUNTER_VERIFY_FANOUT);
+        T.a++; T.b += bounds[k + 1] - bounds[k];
         return slice(bounds[k], bounds[k + 1] - bounds[k]);
     });
     std::lock_guard<std::mutex> lk(devs[0]->mu);
-    devs[0]->verify_fanout.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    devs[0]->counter(ZKP_HIP_COUNTER_VERIFY_FANOUT).ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }
+
+// What a scheme says about spreading one call: the envelopes' weights as vs_prefix sums (empty: `unit` each), which shards hold what the
+// scheme needs (one flag per candidate; empty: all), and the minimum slice in jobs (~0: no slice is large enough, the call stays put).
+struct VerifyFanout { std::vector<uint64_t> prefix; uint32_t unit = 1; std::vector<uint8_t> holds; uint64_t min_jobs = 1; };
+// The call itself.  slice(lo, m): the scheme's upload plus core on the envelopes [lo, lo + m), on the bound shard.  plan(shards, F): fills the
+// scheme's VerifyFanout; asked only when there are candidates.  The fan-out comes BEFORE any Bind is held: a thread that held its shard while
+// posting to that shard's worker would wait for itself.  One slice: the caller's shard, bound here.
+template <class Plan, class Slice> int verify_call(uint64_t n, Plan plan, Slice slice) {
+    int rc;
+    const std::vector<Device*> shards = verify_fanout_candidates();
+    if (!shards.empty()) {
+        VerifyFanout F; bool fanned = false;
+        if ((rc = plan(shards, F))) return rc;
+        rc = verify_fan_out(shards, F.holds.empty() ? nullptr : F.holds.data(), n, F.prefix.empty() ? nullptr : F.prefix.data(), F.unit, F.min_jobs, slice, &fanned);
+        if (rc || fanned) return rc;
+    }
+    Bind bind;
+    if ((rc = bind.open())) return rc;
+    return slice(0, n);
+}
+// n envelopes of `stride` bytes from host memory on the bound shard's stream: the envelopes, their lengths and up to two uint64 parameter
+// columns (nullptr: none) are copied up, d_ok is n bytes for the verdicts.  `mem` owns the blocks until this object goes out of scope.
+struct EnvelopeUpload {
+    DevScope mem;
+    uint8_t *d_in = nullptr, *d_ok = nullptr; uint32_t* d_len = nullptr; uint64_t *d_p0 = nullptr, *d_p1 = nullptr;
+    int open(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens, const uint64_t* p0 = nullptr, const uint64_t* p1 = nullptr) {
+        hipStream_t st = dev().stream;
+        HIP_TRY(mem.alloc(&d_in, stride * n)); HIP_TRY(mem.alloc(&d_len, 4 * n)); HIP_TRY(mem.alloc(&d_ok, n));
+        if (p0) HIP_TRY(mem.alloc(&d_p0, 8 * n));
+        if (p1) HIP_TRY(mem.alloc(&d_p1, 8 * n));
+        HIP_TRY(hipMemcpyAsync(d_in, proofs, stride * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st));
+        if (p0) HIP_TRY(hipMemcpyAsync(d_p0, p0, 8 * n, hipMemcpyHostToDevice, st));
+        if (p1) HIP_TRY(hipMemcpyAsync(d_p1, p1, 8 * n, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
 
 // workspace carving ---------------------------------------------------------------------------------
 struct Ws {
@@ -1283,9 +1327,8 @@ void zkp_hip_shutdown(void) try {
         for (auto& F : d->fam) { free_set(F.p1); for (auto& s : F.rd) free_set(s); F.ready = false; }
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
-        d->g16_verify = Device::G16VerifyStats();
-        d->self_check = Device::SelfCheckStats();
-        d->verify_fanout = Device::VerifyFanoutStats(); d->verify_mixed = Device::VerifyMixedStats(); d->stark_verify_resident = 0;
+        for (auto& C : d->host) C = Device::HostCounter();
+        d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
         t_dev = prev;
@@ -1305,32 +1348,11 @@ int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint6
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
     for (Device* d : shards) {
-        if (which == ZKP_HIP_COUNTER_G16_VERIFY) {          // host-side counters: no events to collect, and a shard that has not run yet is not initialised for them
+        if (which >= ZKP_HIP_COUNTER_G16_VERIFY) {          // host-side counters: no events to collect, and a shard that has not run yet is not initialised for them
             std::lock_guard<std::mutex> dl(d->mu);
-            Device::G16VerifyStats& V = d->g16_verify;
-            tms += V.ms; tl += V.launches; ta += V.adds;
-            if (reset) V = Device::G16VerifyStats();
-            continue;
-        }
-        if (which == ZKP_HIP_COUNTER_BATCH_SELF_CHECK) {
-            std::lock_guard<std::mutex> dl(d->mu);
-            Device::SelfCheckStats& V = d->self_check;
-            tms += V.ms; tl += V.verified; ta += V.refused;
-            if (reset) V = Device::SelfCheckStats();
-            continue;
-        }
-        if (which == ZKP_HIP_COUNTER_VERIFY_FANOUT) {
-            std::lock_guard<std::mutex> dl(d->mu);
-            Device::VerifyFanoutStats& V = d->verify_fanout;
-            tms += V.ms; tl += V.slices; ta += V.envelopes;
-            if (reset) V = Device::VerifyFanoutStats();
-            continue;
-        }
-        if (which == ZKP_HIP_COUNTER_VERIFY_MIXED) {
-            std::lock_guard<std::mutex> dl(d->mu);
-            Device::VerifyMixedStats& V = d->verify_mixed;
-            tms += V.ms; tl += V.passes; ta += V.rows;
-            if (reset) V = Device::VerifyMixedStats();
+            Device::HostCounter& C = d->counter(which);
+            tms += C.ms; tl += C.a; ta += C.b;
+            if (reset) C = Device::HostCounter();
             continue;
         }
         Bind bind; int rc = bind.open(d);

@@ -57,6 +57,35 @@ def test_absurd_sizes_are_argument_errors_before_anything_is_read():
         assert f(1, None, None, None, None) == -3 and b"null pointer" in L.zkp_hip_last_error()
 
 
+# the six per-scheme host-buffer verify calls: name, number of pointer arguments (n first, stride after the first pointer)
+PER_SCHEME_VERIFY = [("range", 5), ("threshold", 4), ("consistency", 3), ("equality", 3), ("membership", 3), ("improvement", 4)]
+
+
+@pytest.mark.parametrize("name,nptr", PER_SCHEME_VERIFY)
+def test_per_scheme_verify_refusals_and_their_order(name, nptr):
+    """Every refusal below is made before a device is looked for.  The order is part of the contract: a null pointer is reported before
+    the batch size (the mixed call above tests the size first), the stride last."""
+    from libzkp_amd import _native
+    L = ctypes.CDLL(_native.LIB_PATH)
+    L.zkp_hip_last_error.restype = ctypes.c_char_p
+    f = getattr(L, "zkp_hip_verify_%s_batch" % name)
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * (nptr - 1)
+    bufs = [ctypes.create_string_buffer(64) for _ in range(nptr)]
+    valid = [ctypes.addressof(b) for b in bufs]
+
+    def call(n, ptrs, stride=64):
+        return f(n, ptrs[0], stride, *ptrs[1:])
+
+    assert call(0, [None] * nptr) == 0
+    for k in range(nptr):
+        assert call(1, valid[:k] + [None] + valid[k + 1:]) == -3 and b"null pointer" in L.zkp_hip_last_error(), k
+    assert call((1 << 22) + 1, [None] * nptr) == -3 and b"null pointer" in L.zkp_hip_last_error()
+    assert call((1 << 22) + 1, valid) == -3 and b"batch too large" in L.zkp_hip_last_error()
+    assert call((1 << 22) + 1, valid, 0) == -3 and b"batch too large" in L.zkp_hip_last_error()
+    assert call(1, valid, 0) == -3 and b"bad stride" in L.zkp_hip_last_error()
+
+
 def test_cpp_caller_builds_and_fails_loudly_without_gpu():
     """tests/abi/abi_call_verify.cpp calls both entry points through the headers alone.  Here: it compiles and links against the built
     library, names every declared symbol, and -- on a box without a GPU -- reports the missing device instead of computing anything on
