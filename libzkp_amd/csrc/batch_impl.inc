@@ -20,8 +20,6 @@
 // against the ops' staged parameters (batch_self_check.h) and turns a refused envelope into a failed op.
 namespace {
 
-constexpr uint32_t LEN_DYN = 0xffffffffu;
-enum : uint8_t { DYN_NONE = 0, DYN_LEN_STATUS = 1, DYN_LEN_ONLY = 2 };
 struct PackView {
     uint32_t n;
     const uint64_t* src_off;       // [n] byte offset of op i's record in the arena
@@ -107,8 +105,6 @@ __global__ void __launch_bounds__(64) k_self_check_flip(uint8_t* arena, const ui
     if (blockIdx.x == 0 && threadIdx.x == 0) step_self_check_flip(arena, src_off, j, byte);
 }
 
-size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // per-shard scheduler state (Device::batch): two LANES of streams + events, so that two staged batches can be in flight on a
 // shard (a server feeding batch after batch: the tail of one batch -- the last Bulletproofs rounds, the final assemblies -- runs
 // under the MSMs of the next); the pinned input staging buffer
@@ -181,36 +177,11 @@ void batch_release_all() {
     delete B; dev().batch = nullptr;
 }
 
-// One shard's share of a staged batch.
-struct ShardPlan {
+// One shard's share of a staged batch: the host plan (batch_plan.h) and what the shard holds on the device for it.
+struct ShardPlan : StagePlan {
     Device* d = nullptr;
     uint64_t generation = 0;               // of the shard when the device blocks were taken
-    uint32_t n = 0;
-    std::vector<uint32_t> gidx;            // global op index of local op j (ascending)
-    // rows per variant (valid ops only for the variants validated on the host)
-    uint32_t n_range = 0, n_eq = 0, n_mem = 0, n_imp = 0, n_thr = 0, n_con = 0;
-    uint64_t stride_mem = 0, stride_con = 0;
-    HostJobs thrJ, conJ;
-    std::vector<uint8_t> thr_img, con_img;
-    std::vector<uint32_t> con_counts, con_lens;
-    uint64_t max_total = 0;
-    // staging image / device blocks
-    size_t in_bytes = 0, arena_bytes = 0, meta_bytes = 0;
     uint8_t *d_in = nullptr, *d_arena = nullptr, *d_out = nullptr, *d_meta = nullptr;
-    // offsets into d_in
-    size_t i_rv = 0, i_rmin = 0, i_rmax = 0, i_rseed = 0, i_ev = 0, i_eseed = 0, i_mv = 0, i_msets = 0, i_mlen = 0, i_mseed = 0, i_io = 0, i_in = 0,
-           i_tseed = 0, i_cseed = 0, i_ccount = 0, i_clen = 0, i_src = 0, i_lenf = 0, i_dix = 0, i_dkind = 0, i_stf = 0;
-    // offsets into d_arena
-    size_t a_range = 0, a_eq = 0, a_mem = 0, a_imp = 0, a_thr = 0, a_con = 0, a_dlen = 0, a_dst = 0;
-    // offsets into d_meta (results): out_off[n + 1] | status[n] | len[n]
-    size_t m_off = 0, m_status = 0, m_len = 0;
-    // self-check (ZKP_HIP_OP_SELF_CHECK): further offsets into d_in -- the thresholds, every op's variant, the verifiers' lens / verdict rows and
-    // the row <-> op map (written on the device), the two counters -- and the variants' geometry, indexed by op kind
-    bool self_check = false;
-    size_t i_thr = 0, i_var = 0, i_rlen = 0, i_rop = 0, i_rok = 0, i_oprow = 0, i_cnt = 0;
-    uint64_t v_base[SC_KINDS] = {0}, v_stride[SC_KINDS] = {0};
-    uint32_t v_row0[SC_KINDS] = {0}, v_rows[SC_KINDS] = {0};
-    std::vector<uint8_t> op_variant;       // [n] the op's kind when it has an arena row, else 0
     int64_t flip_op = -1; uint32_t flip_byte = 0;      // ZKP_HIP_SELF_CHECK_FLIP as read by the last prove: local op index (-1: none), byte of its record
     bool proved = false;
     hipEvent_t finished = nullptr;         // recorded behind the last kernel of a prove; zkp_hip_batch_wait synchronises on it
@@ -241,8 +212,6 @@ template <class F> int for_each_shard(zkp_hip_batch& B, F f, bool init = true) {
     return for_each_device(devs, [&](size_t k) { return f(B.shards[k]); }, init);
 }
 
-// the op's kind without the batch-wide ZKP_HIP_OP_SELF_CHECK flag: every reader of `kind` goes through this
-uint32_t op_kind(const zkp_hip_op& o) { return o.kind & ~ZKP_HIP_OP_SELF_CHECK; }
 // a batch is self-checked as a whole: *flagged = every op carries the flag; some but not all: ZKP_HIP_E_ARGUMENT
 int self_check_flag(uint64_t n, const zkp_hip_op* ops, bool* flagged) {
     uint64_t with = 0;
@@ -250,17 +219,6 @@ int self_check_flag(uint64_t n, const zkp_hip_op* ops, bool* flagged) {
     if (with != 0 && with != n) return fail(ZKP_HIP_E_ARGUMENT, "self-check is a property of the whole batch: ZKP_HIP_OP_SELF_CHECK must be set on every op of a call or on none");
     if (flagged) *flagged = n != 0 && with == n;
     return 0;
-}
-uint64_t op_max_bytes(const zkp_hip_op& o) {
-    switch (op_kind(o)) {
-        case ZKP_HIP_OP_RANGE: return RANGE_PROOF_BYTES;
-        case ZKP_HIP_OP_EQUALITY: return 298;
-        case ZKP_HIP_OP_THRESHOLD: return threshold_envelope_bytes(6);
-        case ZKP_HIP_OP_MEMBERSHIP: return 10 + 4 + 8ull * (o.count <= G16_MAX_SET ? o.count : 0) + 256 + 32;
-        case ZKP_HIP_OP_IMPROVEMENT: return STARK_MAX_ENVELOPE;
-        case ZKP_HIP_OP_CONSISTENCY: return consistency_envelope_bytes(o.count);
-        default: return 0;
-    }
 }
 int check_ops(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, bool* self_check = nullptr) {
     uint64_t list_total = 0;
@@ -277,84 +235,17 @@ int check_ops(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, bool* se
     return self_check_flag(n, ops, self_check);
 }
 
-// Which shard proves which op: every variant's bucket (ops of one kind, in the caller's order) is cut into `shards` contiguous
-// slices whose sizes differ by at most one, so all GPUs run the same kernel mix (SURVEY 8e).  Pure host logic.
-void plan_shards(uint64_t n, const zkp_hip_op* ops, uint32_t shards, uint32_t* shard_of_op) {
-    uint64_t count[7] = {0, 0, 0, 0, 0, 0, 0}, seen[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (uint64_t i = 0; i < n; i++) count[op_kind(ops[i])]++;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint32_t k = op_kind(ops[i]);
-        const uint64_t q = seen[k]++, m = count[k];
-        // slice s holds bucket positions [m*s/S, m*(s+1)/S): the owner of position q is the largest s with m*s/S <= q
-        uint32_t s = (uint32_t)(((q + 1) * shards - 1) / m);
-        while (s > 0 && m * s / shards > q) s--;
-        while (s + 1 < shards && m * (s + 1) / shards <= q) s++;
-        shard_of_op[i] = s;
-    }
-}
-
-// builds one shard's staging image from its ops (host only), uploads it, and allocates the device blocks
+// one shard's staging: the host plan and image (batch_plan.h), then the device blocks and the one upload
 int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, const uint8_t* seeds, bool self_check) {
-    const uint32_t n = P.n;
-    P.self_check = self_check;
     BatchState* BS = nullptr; int rc;
     if ((rc = batch_state(&BS))) return rc;
-    // ---- pass 1: count rows per variant, validate what the host validates
-    std::vector<uint8_t> row_ok(n, 1);
-    P.stride_mem = 0; P.stride_con = 0; P.max_total = 0;
-    for (uint32_t j = 0; j < n; j++) {
-        const zkp_hip_op& o = ops[P.gidx[j]];
-        P.max_total += op_max_bytes(o);
-        switch (op_kind(o)) {
-            case ZKP_HIP_OP_RANGE: P.n_range++; break;
-            case ZKP_HIP_OP_EQUALITY: row_ok[j] = equality_ok(o.a, o.b); P.n_eq += row_ok[j]; break;
-            case ZKP_HIP_OP_MEMBERSHIP:
-                row_ok[j] = membership_ok(o.a, lists + o.list_off, o.count); P.n_mem += row_ok[j];
-                if (row_ok[j] && op_max_bytes(o) > P.stride_mem) P.stride_mem = op_max_bytes(o);
-                break;
-            case ZKP_HIP_OP_IMPROVEMENT: row_ok[j] = improvement_ok(o.a, o.b); P.n_imp += row_ok[j]; break;
-            case ZKP_HIP_OP_THRESHOLD: P.n_thr++; break;
-            default: P.n_con++; if (consistency_envelope_bytes(o.count ? o.count : 1) > P.stride_con) P.stride_con = consistency_envelope_bytes(o.count ? o.count : 1); break;
-        }
-    }
+    plan_stage_layout(P, ops, lists, self_check);
+    const VariantPlan* V = P.var;
     // a shard that holds only a verifying key for a circuit cannot prove its ops: said here, before anything is allocated or uploaded
-    if (P.n_eq && g16s().key[G16_EQUALITY].verifier_only()) return no_proving_key(g16s().key[G16_EQUALITY]);
-    if (P.n_mem && g16s().key[G16_MEMBERSHIP].verifier_only()) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
+    if (V[ZKP_HIP_OP_EQUALITY].rows && g16s().key[G16_EQUALITY].verifier_only()) return no_proving_key(g16s().key[G16_EQUALITY]);
+    if (V[ZKP_HIP_OP_MEMBERSHIP].rows && g16s().key[G16_MEMBERSHIP].verifier_only()) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
     // the generator tables are built here, not at launch, when ZKP_HIP_ED_TABLES=lazy left them for the first batch that needs them
-    if ((P.n_range || P.n_thr || P.n_con) && (rc = ensure_bp())) return rc;
-    // ---- layout of the staging image, the arena and the result block
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += pad256(bytes); return o; };
-    P.i_rv = take(8ull * P.n_range); P.i_rmin = take(8ull * P.n_range); P.i_rmax = take(8ull * P.n_range); P.i_rseed = take(32ull * P.n_range);
-    P.i_ev = take(8ull * P.n_eq); P.i_eseed = take(32ull * P.n_eq);
-    P.i_mv = take(8ull * P.n_mem); P.i_msets = take(8ull * G16_MAX_SET * P.n_mem); P.i_mlen = take(4ull * P.n_mem); P.i_mseed = take(32ull * P.n_mem);
-    P.i_io = take(8ull * P.n_imp); P.i_in = take(8ull * P.n_imp);
-    P.i_tseed = take(32ull * P.n_thr); P.i_cseed = take(32ull * P.n_con); P.i_ccount = take(4ull * P.n_con); P.i_clen = take(4ull * P.n_con);
-    P.i_src = take(8ull * n); P.i_lenf = take(4ull * n); P.i_dix = take(4ull * n); P.i_dkind = take(n); P.i_stf = take(4ull * n);
-    const uint64_t stride_thr = threshold_envelope_bytes(6);
-    if (self_check) {
-        // what the verifier cores need beside the prover's inputs: the thresholds (the prover takes them through the framing), and rows of
-        // lens / verdicts per variant, built on the device (k_self_check_rows); a variant's rows start at a multiple of SC_ROW_ALIGN
-        const uint32_t rows[SC_KINDS] = {0, P.n_range, P.n_eq, P.n_thr, P.n_mem, P.n_imp, P.n_con};
-        uint32_t total = 0;
-        for (uint32_t k = 0; k < SC_KINDS; k++) { P.v_row0[k] = total; P.v_rows[k] = rows[k]; total += (rows[k] + SC_ROW_ALIGN - 1) / SC_ROW_ALIGN * SC_ROW_ALIGN; }
-        P.i_thr = take(8ull * P.n_thr); P.i_var = take(n); P.i_rlen = take(4ull * total); P.i_rop = take(4ull * total); P.i_rok = take(total);
-        P.i_oprow = take(4ull * n); P.i_cnt = take(8);
-    }
-    P.in_bytes = off;
-    off = 0;
-    P.a_range = take((size_t)RANGE_PROOF_BYTES * P.n_range); P.a_eq = take(298ull * P.n_eq); P.a_mem = take(P.stride_mem * P.n_mem);
-    P.a_imp = take((size_t)STARK_MAX_ENVELOPE * P.n_imp); P.a_thr = take(stride_thr * P.n_thr); P.a_con = take(P.stride_con * P.n_con);
-    P.a_dlen = take(4ull * (P.n_range + P.n_imp)); P.a_dst = take(4ull * P.n_range);
-    P.arena_bytes = off;
-    {
-        const uint64_t base[SC_KINDS] = {0, P.a_range, P.a_eq, P.a_thr, P.a_mem, P.a_imp, P.a_con};
-        const uint64_t stride[SC_KINDS] = {0, RANGE_PROOF_BYTES, 298, stride_thr, P.stride_mem, STARK_MAX_ENVELOPE, P.stride_con};
-        for (uint32_t k = 0; k < SC_KINDS; k++) { P.v_base[k] = base[k]; P.v_stride[k] = stride[k]; }
-    }
-    off = 0;
-    P.m_off = take(8ull * (n + 1)); P.m_status = take(4ull * n); P.m_len = take(4ull * n);
-    P.meta_bytes = off;
+    if ((V[ZKP_HIP_OP_RANGE].rows || V[ZKP_HIP_OP_THRESHOLD].rows || V[ZKP_HIP_OP_CONSISTENCY].rows) && (rc = ensure_bp())) return rc;
     // ---- pinned staging image
     if (P.in_bytes > BS->h_in_cap) {
         if (BS->h_in) { HIP_TRY(hipHostFree(BS->h_in)); BS->h_in = nullptr; BS->h_in_cap = 0; }
@@ -362,77 +253,7 @@ int stage_shard(ShardPlan& P, const zkp_hip_op* ops, const uint64_t* lists, cons
         HIP_TRY(hipHostMalloc(&BS->h_in, cap, hipHostMallocDefault)); BS->h_in_cap = cap;
     }
     uint8_t* h = (uint8_t*)BS->h_in;
-    auto u64p = [&](size_t o) { return reinterpret_cast<uint64_t*>(h + o); };
-    auto u32p = [&](size_t o) { return reinterpret_cast<uint32_t*>(h + o); };
-    uint64_t* src = u64p(P.i_src); uint32_t* lenf = u32p(P.i_lenf); uint32_t* dix = u32p(P.i_dix); uint8_t* dkind = h + P.i_dkind;
-    int32_t* stf = reinterpret_cast<int32_t*>(h + P.i_stf);
-    // threshold / consistency inputs gathered for the framing helpers
-    std::vector<uint64_t> t_vals, t_thr, c_vals; std::vector<uint32_t> t_counts, c_counts, t_at, c_at;
-    uint32_t r = 0, e = 0, m = 0, s = 0;
-    for (uint32_t j = 0; j < n; j++) {
-        const uint64_t gi = P.gidx[j];
-        const zkp_hip_op& o = ops[gi];
-        const uint8_t* sd = seeds + 32 * gi;
-        src[j] = 0; lenf[j] = 0; dix[j] = 0; dkind[j] = DYN_NONE; stf[j] = row_ok[j] ? ZKP_HIP_OK : ZKP_HIP_INVALID_INPUT;
-        switch (op_kind(o)) {
-            case ZKP_HIP_OP_RANGE:
-                u64p(P.i_rv)[r] = o.a; u64p(P.i_rmin)[r] = o.b; u64p(P.i_rmax)[r] = o.c; memcpy(h + P.i_rseed + 32ull * r, sd, 32);
-                src[j] = P.a_range + (uint64_t)RANGE_PROOF_BYTES * r; lenf[j] = LEN_DYN; dix[j] = r; dkind[j] = DYN_LEN_STATUS; r++;
-                break;
-            case ZKP_HIP_OP_EQUALITY:
-                if (!row_ok[j]) break;
-                u64p(P.i_ev)[e] = o.a; memcpy(h + P.i_eseed + 32ull * e, sd, 32);
-                src[j] = P.a_eq + 298ull * e; lenf[j] = 298; e++;
-                break;
-            case ZKP_HIP_OP_MEMBERSHIP:
-                if (!row_ok[j]) break;
-                u64p(P.i_mv)[m] = o.a; u32p(P.i_mlen)[m] = o.count; memcpy(h + P.i_mseed + 32ull * m, sd, 32);
-                for (uint32_t k = 0; k < G16_MAX_SET; k++) u64p(P.i_msets)[(size_t)G16_MAX_SET * m + k] = k < o.count ? lists[o.list_off + k] : 0;
-                src[j] = P.a_mem + P.stride_mem * m; lenf[j] = (uint32_t)op_max_bytes(o); m++;
-                break;
-            case ZKP_HIP_OP_IMPROVEMENT:
-                if (!row_ok[j]) break;
-                u64p(P.i_io)[s] = o.a; u64p(P.i_in)[s] = o.b;
-                src[j] = P.a_imp + (uint64_t)STARK_MAX_ENVELOPE * s; lenf[j] = LEN_DYN; dix[j] = P.n_range + s; dkind[j] = DYN_LEN_ONLY; s++;
-                break;
-            case ZKP_HIP_OP_THRESHOLD:
-                memcpy(h + P.i_tseed + 32ull * t_at.size(), sd, 32);
-                t_thr.push_back(o.a); t_counts.push_back(o.count); t_vals.insert(t_vals.end(), lists + o.list_off, lists + o.list_off + o.count);
-                t_at.push_back(j);
-                break;
-            default:
-                memcpy(h + P.i_cseed + 32ull * c_at.size(), sd, 32);
-                c_counts.push_back(o.count); c_vals.insert(c_vals.end(), lists + o.list_off, lists + o.list_off + o.count);
-                c_at.push_back(j);
-                break;
-        }
-    }
-    if (P.n_thr) {
-        P.thr_img.assign(stride_thr * P.n_thr, 0);
-        std::vector<uint32_t> lens(P.n_thr); std::vector<int32_t> st(P.n_thr);
-        (void)frame_threshold(P.n_thr, t_vals.data(), t_counts.data(), t_thr.data(), 6, P.thr_img.data(), stride_thr, lens.data(), st.data(), P.thrJ);
-        for (uint32_t k = 0; k < P.n_thr; k++) { const uint32_t j = t_at[k]; src[j] = P.a_thr + stride_thr * k; lenf[j] = lens[k]; stf[j] = st[k]; }
-    }
-    if (P.n_con) {
-        P.con_img.assign(P.stride_con * P.n_con, 0);
-        P.con_lens.assign(P.n_con, 0); std::vector<int32_t> st(P.n_con);
-        (void)frame_consistency(P.n_con, c_vals.data(), c_counts.data(), P.con_img.data(), P.stride_con, P.con_lens.data(), st.data(), P.conJ);
-        P.con_counts = c_counts;
-        for (uint32_t k = 0; k < P.n_con; k++) {
-            const uint32_t j = c_at[k]; src[j] = P.a_con + P.stride_con * k; lenf[j] = P.con_lens[k]; stf[j] = st[k];
-            u32p(P.i_ccount)[k] = c_counts[k]; u32p(P.i_clen)[k] = P.con_lens[k];
-        }
-    }
-    if (self_check) {
-        P.op_variant.assign(n, 0);
-        for (uint32_t j = 0; j < n; j++) {
-            const uint32_t k = op_kind(ops[P.gidx[j]]);
-            const bool validated_on_host = k == ZKP_HIP_OP_EQUALITY || k == ZKP_HIP_OP_MEMBERSHIP || k == ZKP_HIP_OP_IMPROVEMENT;      // (their rows hold valid ops only)
-            P.op_variant[j] = validated_on_host && !row_ok[j] ? 0 : (uint8_t)k;
-        }
-        if (n) memcpy(h + P.i_var, P.op_variant.data(), n);
-        if (P.n_thr) memcpy(h + P.i_thr, t_thr.data(), 8ull * P.n_thr);
-    }
+    fill_stage_image(P, ops, lists, seeds, h);
     // ---- device blocks + the one upload
     DevPool& pool = dev().pool;
     P.generation = dev().generation;
@@ -467,16 +288,28 @@ int launch_shard_enqueue(ShardPlan& P) {
     BatchLane& LN = BS->lane[lane_ix];
     hipStream_t st = LN.main;
     uint8_t *in = P.d_in, *ar = P.d_arena;
+    const VariantPlan &R = P.var[ZKP_HIP_OP_RANGE], &E = P.var[ZKP_HIP_OP_EQUALITY], &T = P.var[ZKP_HIP_OP_THRESHOLD], &M = P.var[ZKP_HIP_OP_MEMBERSHIP],
+                      &I = P.var[ZKP_HIP_OP_IMPROVEMENT], &C = P.var[ZKP_HIP_OP_CONSISTENCY];
     trace_origin(st);
     if (P.arena_bytes) HIP_TRY(hipMemsetAsync(ar, 0, P.arena_bytes, st));
-    if (P.n_thr) HIP_TRY(hipMemcpyAsync(ar + P.a_thr, P.thr_img.data(), P.thr_img.size(), hipMemcpyHostToDevice, st));
-    if (P.n_con) HIP_TRY(hipMemcpyAsync(ar + P.a_con, P.con_img.data(), P.con_img.size(), hipMemcpyHostToDevice, st));
+    if (T.rows) HIP_TRY(hipMemcpyAsync(ar + T.arena, P.thr_img.data(), P.thr_img.size(), hipMemcpyHostToDevice, st));
+    if (C.rows) HIP_TRY(hipMemcpyAsync(ar + C.arena, P.con_img.data(), P.con_img.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(LN.go, st));
     bool used[4] = {false, false, false, false};
+    // a variant's launches on variant stream k of the lane: behind LN.go, LN.done[k] recorded behind them
+    auto on_stream = [&](int k, auto body) -> int {
+        hipStream_t s = nullptr; used[k] = true;
+        int rcs;
+        if ((rcs = lane_stream(*BS, k, &s))) return rcs;
+        HIP_TRY(hipStreamWaitEvent(s, LN.go, 0));
+        if ((rcs = body(s))) return rcs;
+        HIP_TRY(hipEventRecord(LN.done[k], s));
+        return 0;
+    };
     // Host order of the variants' launches: the Bulletproofs chain (about 50 dependent launches, the long pole of a mixed batch) and the
     // STARK first, then the Groth16 pipelines.  Against Groth16 first, medians are equal (15.9 ms per 4096-op mixed batch), the better
     // runs are 4-6 % better this way (14.4-15.0 against 15.3-15.5 ms over three pairs of 21 runs).
-    if (P.n_range || P.n_thr || P.n_con) {
+    if (R.rows || T.rows || C.rows) {
         // Beside Groth16 work the chain's MSM waves issue ahead of the G1 / G2 gather waves they share SIMDs with: the Groth16 pipelines
         // finish ~1.4 ms before the chain does (DESIGN R4.6), so the chain is the one to favour.  Measured (one box, 11-run medians, alternating
         // runs, not raised / raised): mixed batch of 512 ops 4.79 / 4.57 ms, 2048 7.94 / 7.76, 4096 12.54 / 12.34, 16 384 41.6 / 40.4
@@ -485,46 +318,33 @@ int launch_shard_enqueue(ShardPlan& P) {
         // (156 -> 168 VGPRs with 32 spilled) and a range-only batch 2.7 %.
         static const int edg_prio = env_int("ZKP_HIP_EDG_PRIORITY", 1);
         struct PrioScope { int& r; PrioScope(int& ref, int v) : r(ref) { r = v; } ~PrioScope() { r = 0; } };      // reset on every return
-        PrioScope prio(dev().msm_prio_now, (P.n_eq + P.n_mem) && edg_prio ? 1 : 0);
+        PrioScope prio(dev().msm_prio_now, (E.rows + M.rows) && edg_prio ? 1 : 0);
         SubBatch& jobs_sb = dev().sub[0];      // streams + workspace of the host-described job lists
-        hipStream_t s = nullptr; used[0] = true;
-        if ((rc = lane_stream(*BS, 0, &s))) return rc;
-        HIP_TRY(hipStreamWaitEvent(s, LN.go, 0));
-        if (P.n_range) {
-            if ((rc = prove_range_device_locked(P.n_range, (const uint64_t*)(in + P.i_rv), (const uint64_t*)(in + P.i_rmin), (const uint64_t*)(in + P.i_rmax), 6, in + P.i_rseed,
-                                                ar + P.a_range, RANGE_PROOF_BYTES, (uint32_t*)(ar + P.a_dlen), (int32_t*)(ar + P.a_dst), s, nullptr, (int)lane_ix))) return rc;
-        }
-        if (P.n_thr && (rc = run_jobs_on(jobs_sb, P.thrJ, in + P.i_tseed, ar + P.a_thr, 6, s))) return rc;
-        if (P.n_con) {
-            if ((rc = run_jobs_on(jobs_sb, P.conJ, in + P.i_cseed, ar + P.a_con, 6, s))) return rc;
-            k_consistency_digest<<<(P.n_con + 63) / 64, 64, 0, s>>>(ar + P.a_con, P.stride_con, (const uint32_t*)(in + P.i_ccount), (const uint32_t*)(in + P.i_clen), P.n_con);
-        }
-        HIP_TRY(hipEventRecord(LN.done[0], s));
+        if ((rc = on_stream(0, [&](hipStream_t s) -> int {
+                int rcb;
+                if (R.rows && (rcb = prove_range_device_locked(R.rows, (const uint64_t*)(in + P.i_rv), (const uint64_t*)(in + P.i_rmin), (const uint64_t*)(in + P.i_rmax), 6, in + P.i_rseed,
+                                                               ar + R.arena, R.stride, (uint32_t*)(ar + P.a_dlen), (int32_t*)(ar + P.a_dst), s, nullptr, (int)lane_ix))) return rcb;
+                if (T.rows && (rcb = run_jobs_on(jobs_sb, P.thrJ, in + P.i_tseed, ar + T.arena, 6, s))) return rcb;
+                if (C.rows) {
+                    if ((rcb = run_jobs_on(jobs_sb, P.conJ, in + P.i_cseed, ar + C.arena, 6, s))) return rcb;
+                    k_consistency_digest<<<(C.rows + 63) / 64, 64, 0, s>>>(ar + C.arena, C.stride, (const uint32_t*)(in + P.i_ccount), (const uint32_t*)(in + P.i_clen), C.rows);
+                }
+                return 0;
+            }))) return rc;
     }
-    if (P.n_imp) {
-        hipStream_t s = nullptr; used[3] = true;
-        if ((rc = lane_stream(*BS, 3, &s))) return rc;
-        HIP_TRY(hipStreamWaitEvent(s, LN.go, 0));
-        if ((rc = ensure_stark_constants())) return rc;
-        ZKP_TRACED("k_stark_prove", s, stark_launch_prove((const uint64_t*)(in + P.i_io), (const uint64_t*)(in + P.i_in), P.n_imp, g_stark_const, ar + P.a_imp, STARK_MAX_ENVELOPE,
-                                                          (uint32_t*)(ar + P.a_dlen) + P.n_range, s));
-        HIP_TRY(hipEventRecord(LN.done[3], s));
-    }
-    if (P.n_mem) {
-        hipStream_t s = nullptr; used[2] = true;
-        if ((rc = lane_stream(*BS, 2, &s))) return rc;
-        HIP_TRY(hipStreamWaitEvent(s, LN.go, 0));
-        if ((rc = run_g16(G16_MEMBERSHIP, P.n_mem, (const uint64_t*)(in + P.i_mv), (const uint64_t*)(in + P.i_msets), (const uint32_t*)(in + P.i_mlen), in + P.i_mseed,
-                          ar + P.a_mem, P.stride_mem, s, lane_ix))) return rc;
-        HIP_TRY(hipEventRecord(LN.done[2], s));
-    }
-    if (P.n_eq) {
-        hipStream_t s = nullptr; used[1] = true;
-        if ((rc = lane_stream(*BS, 1, &s))) return rc;
-        HIP_TRY(hipStreamWaitEvent(s, LN.go, 0));
-        if ((rc = run_g16(G16_EQUALITY, P.n_eq, (const uint64_t*)(in + P.i_ev), nullptr, nullptr, in + P.i_eseed, ar + P.a_eq, 298, s, lane_ix))) return rc;
-        HIP_TRY(hipEventRecord(LN.done[1], s));
-    }
+    if (I.rows && (rc = on_stream(3, [&](hipStream_t s) -> int {
+            if (const int rcb = ensure_stark_constants()) return rcb;
+            ZKP_TRACED("k_stark_prove", s, stark_launch_prove((const uint64_t*)(in + P.i_io), (const uint64_t*)(in + P.i_in), I.rows, g_stark_const, ar + I.arena, I.stride,
+                                                              (uint32_t*)(ar + P.a_dlen) + R.rows, s));
+            return 0;
+        }))) return rc;
+    if (M.rows && (rc = on_stream(2, [&](hipStream_t s) {
+            return run_g16(G16_MEMBERSHIP, M.rows, (const uint64_t*)(in + P.i_mv), (const uint64_t*)(in + P.i_msets), (const uint32_t*)(in + P.i_mlen), in + P.i_mseed,
+                           ar + M.arena, M.stride, s, lane_ix);
+        }))) return rc;
+    if (E.rows && (rc = on_stream(1, [&](hipStream_t s) {
+            return run_g16(G16_EQUALITY, E.rows, (const uint64_t*)(in + P.i_ev), nullptr, nullptr, in + P.i_eseed, ar + E.arena, E.stride, s, lane_ix);
+        }))) return rc;
     for (int k = 0; k < 4; k++) if (used[k]) HIP_TRY(hipStreamWaitEvent(st, LN.done[k], 0));
     const PackView V = pack_view(P);
     if (n && P.self_check) {
@@ -543,8 +363,8 @@ int launch_shard_enqueue(ShardPlan& P) {
 int launch_shard(ShardPlan& P) {
     if (P.generation != dev().generation) return fail(ZKP_HIP_E_ARGUMENT, "the batch was staged before zkp_hip_shutdown: stage it again");
     // nothing is enqueued unless every key the batch needs is there (a later variant failing would leave the earlier chains running)
-    if (P.n_eq && !g16s().key[G16_EQUALITY].loaded) return no_proving_key(g16s().key[G16_EQUALITY]);
-    if (P.n_mem && !g16s().key[G16_MEMBERSHIP].loaded) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
+    if (P.var[ZKP_HIP_OP_EQUALITY].rows && !g16s().key[G16_EQUALITY].loaded) return no_proving_key(g16s().key[G16_EQUALITY]);
+    if (P.var[ZKP_HIP_OP_MEMBERSHIP].rows && !g16s().key[G16_MEMBERSHIP].loaded) return no_proving_key(g16s().key[G16_MEMBERSHIP]);
     const int rc = launch_shard_enqueue(P);
     if (rc) {                                     // part of the batch may be running on the lane's streams: the caller is about to hand
         const std::string keep = t_err;           // the shard's blocks back to the pool, so nothing may still be writing them
@@ -565,7 +385,7 @@ int self_check_shard(ShardPlan& P) {
     SelfCheckView V{};
     V.n = n; V.src_off = W.src_off; V.len_fixed = W.len_fixed; V.dyn_ix = W.dyn_ix; V.dyn_kind = W.dyn_kind; V.status_fixed = W.status_fixed;
     V.dyn_len = W.dyn_len; V.dyn_status = W.dyn_status; V.op_variant = in + P.i_var;
-    for (uint32_t k = 0; k < SC_KINDS; k++) { V.base[k] = P.v_base[k]; V.stride[k] = P.v_stride[k]; V.row0[k] = P.v_row0[k]; V.rows[k] = P.v_rows[k]; }
+    for (uint32_t k = 0; k < SC_KINDS; k++) { V.base[k] = P.var[k].arena; V.stride[k] = P.var[k].stride; V.row0[k] = P.var[k].row0; V.rows[k] = P.var[k].rows; }
     V.row_len = (uint32_t*)(in + P.i_rlen); V.row_op = (uint32_t*)(in + P.i_rop); V.row_ok = in + P.i_rok; V.op_row = (uint32_t*)(in + P.i_oprow);
     V.len = W.len; V.status = W.status;
     V.arena = ar; V.eq_value = (const uint64_t*)(in + P.i_ev); V.mem_sets = (const uint64_t*)(in + P.i_msets); V.mem_len = (const uint32_t*)(in + P.i_mlen);
@@ -575,10 +395,10 @@ int self_check_shard(ShardPlan& P) {
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, st));
     k_self_check_rows<<<(n + 255) / 256, 256, 0, st>>>(V);
     HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> jobs(P.n_con);          // k - 1 range proofs for a framed list of k values (none for a list the framing refused)
-    for (uint32_t k = 0; k < P.n_con; k++) jobs[k] = P.con_lens[k] && P.con_counts[k] ? P.con_counts[k] - 1 : 0;
+    std::vector<uint32_t> jobs(P.var[ZKP_HIP_OP_CONSISTENCY].rows);          // k - 1 range proofs for a framed list of k values (none for a list the framing refused)
+    for (uint32_t k = 0; k < jobs.size(); k++) jobs[k] = P.con_lens[k] && P.con_counts[k] ? P.con_counts[k] - 1 : 0;
     SchemePass K[SC_KINDS];
-    for (uint32_t k = 0; k < SC_KINDS; k++) { K[k].n = P.v_rows[k]; K[k].rows = ar + P.v_base[k]; K[k].stride = P.v_stride[k]; K[k].lens = V.row_len + P.v_row0[k]; K[k].ok = V.row_ok + P.v_row0[k]; }
+    for (uint32_t k = 0; k < SC_KINDS; k++) { const VariantPlan& v = P.var[k]; K[k].n = v.rows; K[k].rows = ar + v.arena; K[k].stride = v.stride; K[k].lens = V.row_len + v.row0; K[k].ok = V.row_ok + v.row0; }
     K[ZKP_HIP_OP_RANGE].p0 = (const uint64_t*)(in + P.i_rmin); K[ZKP_HIP_OP_RANGE].p1 = (const uint64_t*)(in + P.i_rmax);
     K[ZKP_HIP_OP_THRESHOLD].p0 = (const uint64_t*)(in + P.i_thr);
     K[ZKP_HIP_OP_IMPROVEMENT].p0 = (const uint64_t*)(in + P.i_io);
@@ -588,7 +408,7 @@ int self_check_shard(ShardPlan& P) {
             const int brc = ensure_mimc_dev();
             if (brc) return brc;
             V.mimc_c = g16s().mimc_dev;
-            k_self_check_bind_g16<<<(P.n_eq + P.n_mem + 63) / 64, 64, 0, st>>>(V);
+            k_self_check_bind_g16<<<(V.rows[ZKP_HIP_OP_EQUALITY] + V.rows[ZKP_HIP_OP_MEMBERSHIP] + 63) / 64, 64, 0, st>>>(V);
             HIP_TRY(hipGetLastError());
             return 0;
         }))) return rc;
@@ -697,7 +517,7 @@ int read_self_check_flip(zkp_hip_batch& B) {
         if (it == P.gidx.end() || *it != (uint32_t)op) continue;
         const uint32_t j = (uint32_t)(it - P.gidx.begin()), k = P.op_variant[j];
         if (k == 0) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the op was refused by validation and has no arena record");
-        if (byte >= P.v_stride[k]) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the byte offset is beyond the op's arena record");
+        if (byte >= P.var[k].stride) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_SELF_CHECK_FLIP: the byte offset is beyond the op's arena record");
         P.flip_op = j; P.flip_byte = (uint32_t)byte;
     }
     return 0;

@@ -557,7 +557,7 @@ int prove_g16_host(int kind, uint64_t n, const uint64_t* values, const uint64_t*
             idx.push_back((uint32_t)i); v.push_back(values[i]);
             sd.insert(sd.end(), seeds + 32 * i, seeds + 32 * i + 32);
             if (kind == G16_MEMBERSHIP) { sl.push_back(cnt); for (uint32_t k = 0; k < G16_MAX_SET; k++) sv.push_back(k < cnt ? sets_flat[pos + k] : 0); }
-            const uint32_t plen = kind == G16_EQUALITY ? 298u : 10u + 4u + 8u * cnt + 256u + 32u;
+            const uint32_t plen = kind == G16_EQUALITY ? EQUALITY_ENVELOPE_BYTES : (uint32_t)membership_envelope_bytes(cnt);
             if (plen > stride) return fail(ZKP_HIP_E_ARGUMENT, "stride too small for the proof envelope");
             out_len[i] = plen; status[i] = ZKP_HIP_OK;
         } else { out_len[i] = 0; status[i] = ZKP_HIP_INVALID_INPUT; any = 1; }
@@ -864,7 +864,7 @@ int zkp_hip_prove_equality_batch(uint64_t n, const uint64_t* val1, const uint64_
                                  uint8_t* out, uint64_t stride, uint32_t* out_len, int32_t* status) try {
     if (n == 0) return 0;
     std::vector<uint8_t> fresh;
-    int rc = prover_args(fresh, seeds, n, {val1, val2, out, out_len, status}, nullptr, stride, 298, "stride must be >= 298");
+    int rc = prover_args(fresh, seeds, n, {val1, val2, out, out_len, status}, nullptr, stride, EQUALITY_ENVELOPE_BYTES, "stride must be >= 298");
     if (rc) return rc;
     std::vector<uint8_t> valid(n);
     for (uint64_t i = 0; i < n; i++) valid[i] = equality_ok(val1[i], val2[i]);

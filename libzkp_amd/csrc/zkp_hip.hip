@@ -37,6 +37,7 @@
 #include "bpv_launch.h"
 #include "edg_launch.h"
 #include "batch_self_check.h"
+#include "batch_plan.h"
 #include "verify_shards.h"
 #include "venv_steps.h"
 #include "../../include/libzkp_hip_verify.h"
@@ -1083,21 +1084,6 @@ int prove_range_device_locked(uint64_t n, const uint64_t* d_value, const uint64_
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Host-described jobs (threshold / consistency framings have variable-length inputs, so their job lists are built on
-// the host: pure bookkeeping, bulletproofs.rs:309-437).  The proving itself is the same device pipeline.
-struct HostJobs {
-    std::vector<uint64_t> v, proof_off, commit_off, ct_v, ct_off;
-    std::vector<uint32_t> seed_ix, proof_ix, ct_seed_ix, ct_bl_ix;
-    std::vector<int32_t> bl_plus, bl_minus;
-    std::vector<uint8_t> kind;
-    void add_job(uint64_t val, uint32_t seed, uint32_t pidx, int32_t plus, int32_t minus, uint8_t k, uint64_t poff, uint64_t coff) {
-        v.push_back(val); seed_ix.push_back(seed); proof_ix.push_back(pidx); bl_plus.push_back(plus); bl_minus.push_back(minus);
-        kind.push_back(k); proof_off.push_back(poff); commit_off.push_back(coff);
-    }
-    void add_commit(uint64_t val, uint32_t seed, uint32_t bl, uint64_t off) { ct_v.push_back(val); ct_seed_ix.push_back(seed); ct_bl_ix.push_back(bl); ct_off.push_back(off); }
-};
-
 // Uploads a host-built job list into the workspace of `sb` and runs the prover on `st`.  d_img: device image that already
 // holds every framing byte (proof_off / commit_off / ct_off are offsets into it); d_seeds: 32 bytes per seed index.
 // The job arrays of H must stay alive until `st` has passed the copies (callers keep H until they synchronise).
@@ -1138,8 +1124,6 @@ int run_host_jobs(const HostJobs& H, const uint8_t* seeds, size_t nseeds, uint8_
     return rc;
 }
 
-void put_le_host(uint8_t* p, uint64_t x, int n) { for (int i = 0; i < n; i++) p[i] = (uint8_t)(x >> (8 * i)); }
-
 int fresh_seeds(std::vector<uint8_t>& buf, size_t n) {
     buf.resize(32 * n);
     size_t got = 0;
@@ -1173,78 +1157,6 @@ int prover_args(std::vector<uint8_t>& fresh, const uint8_t*& seeds, uint64_t n, 
 }
 // a verifier's: envelopes of `stride` bytes, zero refused
 int verifier_args(uint64_t n, std::initializer_list<const void*> ptrs, uint64_t stride) { return host_args(n, ptrs, nullptr, stride, 1, "bad stride"); }
-
-// The reference's validation rules (utils/validation.rs), one predicate each, for the per-variant entry points and the batch scheduler
-// (stage_shard) alike.  The threshold rule is frame_threshold's.
-bool equality_ok(uint64_t a, uint64_t b) { return a == b; }                                 // validation.rs:21-26
-bool membership_ok(uint64_t value, const uint64_t* set, uint32_t count) {                 // validation.rs:47-60; sets of at most 64 (snark.rs:406-418)
-    if (count == 0 || count > G16_MAX_SET) return false;
-    for (uint32_t k = 0; k < count; k++) if (set[k] == value) return true;
-    return false;
-}
-bool improvement_ok(uint64_t old_value, uint64_t new_value) { return new_value > old_value; }     // validation.rs:63-71
-bool consistency_ok(const uint64_t* list, uint32_t count) {                                  // validation.rs:74-86: not empty, non-decreasing
-    if (count == 0) return false;
-    for (uint32_t j = 1; j < count; j++) if (list[j - 1] > list[j]) return false;
-    return true;
-}
-
-uint64_t threshold_envelope_bytes(uint32_t lg) { return 10 + 8 + 4 + 4 + rp_bytes(lg) + 32 + 32; }      // 762 for n_bits = 64
-uint64_t consistency_envelope_bytes(uint32_t count) {
-    if (count == 0) return 0;
-    return 10 + 4 + 32ull * count + (uint64_t)(4 + RP_BYTES) * (count - 1) + 32ull * (count - 1) + 32;
-}
-// Framing of threshold proofs (threshold_proof.rs:12-32 -> bulletproofs.rs:309-366): validates every op, writes the envelope
-// and body framing of the valid ones into `img` (n records of `stride` bytes, zeroed by the caller) and appends one proof
-// job + one commitment task per valid op; seed index = op index.  Returns 1 if any op is invalid.
-int frame_threshold(uint64_t n, const uint64_t* values, const uint32_t* counts, const uint64_t* thresholds, uint32_t lg,
-                    uint8_t* img, uint64_t stride, uint32_t* out_len, int32_t* status, HostJobs& H) {
-    const uint32_t RP = rp_bytes(lg), n_bits = 1u << lg;
-    const uint64_t PB = threshold_envelope_bytes(lg);
-    const uint64_t max_diff = lg >= 6 ? ~0ull : (1ull << (1u << lg)) - 1;   // bulletproofs.rs:330-336
-    int any = 0; size_t pos = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        // validation.rs:30-47 / bulletproofs.rs:314-336
-        bool ok = counts[i] > 0; uint64_t sum = 0;
-        for (uint32_t k = 0; k < counts[i] && ok; k++) { const uint64_t x = values[pos + k]; if (sum + x < sum) ok = false; sum += x; }
-        pos += counts[i];
-        if (ok && sum < thresholds[i]) ok = false;
-        if (ok && sum - thresholds[i] > max_diff) ok = false;
-        status[i] = ok ? ZKP_HIP_OK : ZKP_HIP_INVALID_INPUT; out_len[i] = ok ? (uint32_t)PB : 0; any |= !ok;
-        if (!ok) continue;
-        uint8_t* o = img + i * stride; const uint64_t base = i * stride;
-        o[0] = 2; o[1] = 3; put_le_host(o + 2, 8 + 4 + 4 + RP + 32, 4); put_le_host(o + 6, 32, 4);
-        put_le_host(o + 10, thresholds[i], 8); put_le_host(o + 18, n_bits, 4); put_le_host(o + 22, RP, 4);
-        H.add_job(sum - thresholds[i], (uint32_t)i, 0, 0, -1, KIND_THRESHOLD, base + 26, base + 26 + RP);
-        H.add_commit(sum, (uint32_t)i, 0, base + 26 + RP + 32);
-    }
-    return any;
-}
-// Framing of consistency proofs (consistency_proof.rs:12-22 -> bulletproofs.rs:368-437): k commitment tasks and k - 1 proof
-// jobs per valid op.  The envelope's commitment field (SHA-256 of the commitment list) is filled in after the device run.
-int frame_consistency(uint64_t n, const uint64_t* data, const uint32_t* counts, uint8_t* img, uint64_t stride, uint32_t* out_len, int32_t* status, HostJobs& H) {
-    int any = 0; size_t pos = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint32_t k = counts[i]; const uint64_t* d = data + pos; pos += k;
-        bool ok = consistency_ok(d, k);
-        const uint64_t need = consistency_envelope_bytes(k);
-        if (ok && need > stride) ok = false;                        // (callers size the stride from the counts; never reached through the ABI)
-        status[i] = ok ? ZKP_HIP_OK : ZKP_HIP_INVALID_INPUT; out_len[i] = ok ? (uint32_t)need : 0; any |= !ok;
-        if (!ok) continue;
-        uint8_t* o = img + i * stride; const uint64_t base = i * stride;
-        const uint64_t body = need - 10 - 32;
-        o[0] = 2; o[1] = 6; put_le_host(o + 2, body, 4); put_le_host(o + 6, 32, 4);
-        put_le_host(o + 10, k, 4);
-        const uint64_t commits = base + 14, proofs = commits + 32ull * k, dcs = proofs + (uint64_t)(4 + RP_BYTES) * (k - 1);
-        for (uint32_t j = 0; j < k; j++) H.add_commit(d[j], (uint32_t)i, j, commits + 32ull * j);
-        for (uint32_t j = 1; j < k; j++) {
-            put_le_host(img + proofs + (uint64_t)(4 + RP_BYTES) * (j - 1), RP_BYTES, 4);
-            H.add_job(d[j] - d[j - 1], (uint32_t)i, j - 1, (int32_t)j, (int32_t)(j - 1), KIND_CONSISTENCY,
-                      proofs + (uint64_t)(4 + RP_BYTES) * (j - 1) + 4, dcs + 32ull * (j - 1));
-        }
-    }
-    return any;
-}
 
 }  // namespace
 // the ed25519 sum launcher under an external name (edg_launch.h): launch_sum_ed above has internal linkage

@@ -50,6 +50,16 @@ best, med = timeit(lambda: L.zkp_hip_batch_prove(h))
 print("mixed %d ops, staged in HBM, proofs left in HBM: best %.2f ms, median %.2f ms -> %.0f proofs/s" % (n, best, med, n / (med * 1e-3)))
 L.zkp_hip_batch_free(h)
 
+
+def stage_alone():
+    hs = ctypes.c_void_p()
+    assert L.zkp_hip_batch_stage(n, P(ops), P(lists), P(seeds), ctypes.byref(hs)) == 0, _native.last_error()
+    L.zkp_hip_batch_free(hs)
+
+
+best, med = timeit(stage_alone)
+print("mixed %d ops, stage alone (zkp_hip_batch_stage + zkp_hip_batch_free; the stage ends in a synchronise): best %.3f ms, median %.3f ms" % (n, best, med))
+
 # the four variants on their own
 sd = seeds.reshape(n, 32)
 parts = {}
