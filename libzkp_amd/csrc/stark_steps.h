@@ -556,14 +556,18 @@ struct StarkReader {
     ZKP_HD const uint8_t* take(uint32_t k) { if (!ok || n - p < k) { ok = false; return b; } const uint8_t* r = b + p; p += k; return r; }
     ZKP_HD uint32_t u8() { const uint8_t* r = take(1); return ok ? r[0] : 0u; }
     ZKP_HD uint32_t u16() { const uint8_t* r = take(2); return ok ? (uint32_t)r[0] | ((uint32_t)r[1] << 8) : 0u; }
-    ZKP_HD uint32_t vint() {                       // winter-utils variable-length usize (values here are < 2^21: at most 3 bytes)
+    // winter-utils variable-length usize, every form read_usize takes (oracle/py/stark.py: read_vint): the trailing zero bits of the first
+    // byte count the bytes that follow it (1 to 8 bytes in all, 7 value bits per byte); a zero first byte is followed by the value's 8 bytes.
+    // The value stays in 64 bits: the callers compare it as it is, nothing is cut to 32 bits first.
+    ZKP_HD uint64_t vint() {
         if (!ok || p >= n) { ok = false; return 0; }
         const uint32_t first = b[p];
-        if (first == 0) { ok = false; return 0; }
-        uint32_t nb = 1; while (((first >> (nb - 1)) & 1u) == 0) nb++;
-        if (nb > 4) { ok = false; return 0; }
+        uint32_t nb = 1;
+        if (first == 0) nb = 9; else while (((first >> (nb - 1)) & 1u) == 0) nb++;
         const uint8_t* r = take(nb); if (!ok) return 0;
-        uint32_t v = 0; for (uint32_t i = 0; i < nb; i++) v |= (uint32_t)r[i] << (8 * i);
+        uint64_t v = 0;
+        if (nb == 9) { for (uint32_t i = 0; i < 8; i++) v |= (uint64_t)r[1 + i] << (8 * i); return v; }
+        for (uint32_t i = 0; i < nb; i++) v |= (uint64_t)r[i] << (8 * i);
         return v >> nb;
     }
     ZKP_HD f128 element() {
@@ -577,11 +581,15 @@ struct StarkReader {
 ZKP_HD inline void ld_digest(uint32_t d[8], const uint8_t* p) { for (int i = 0; i < 8; i++) d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24); }
 struct StarkQueries { f128 val[32]; const uint8_t* list[32]; uint8_t cnt[32]; uint32_t nlists, depth; };
 ZKP_HD_NOINLINE inline void stark_read_queries(StarkReader& r, uint32_t nq, StarkQueries& q) {
-    if (r.vint() != 16 * nq) r.ok = false;
+    if (r.vint() != (uint64_t)16 * nq) r.ok = false;
     for (uint32_t i = 0; i < nq && r.ok; i++) q.val[i] = r.element();
-    const uint32_t olen = r.vint(), end = r.p + olen;
-    q.depth = r.u8(); q.nlists = r.vint();
-    if (q.nlists > 32) r.ok = false;
+    const uint64_t olen = r.vint();
+    if (olen > r.n - r.p) { r.ok = false; q.depth = 0; q.nlists = 0; return; }      // an opening longer than what is left: no sum that could wrap
+    const uint32_t end = r.p + (uint32_t)olen;
+    q.depth = r.u8();
+    const uint64_t nlists = r.vint();
+    if (nlists > 32) r.ok = false;
+    q.nlists = r.ok ? (uint32_t)nlists : 0u;
     for (uint32_t k = 0; k < q.nlists && r.ok; k++) { q.cnt[k] = (uint8_t)r.u8(); q.list[k] = r.take(32u * q.cnt[k]); }
     if (r.p != end) r.ok = false;
 }

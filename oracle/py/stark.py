@@ -392,8 +392,16 @@ def _read_queries(r, count):
     return values, nodes, depth
 
 
-def verify(proof, old, new):
-    """winterfell::verify restated for this AIR (stark.rs:190-211): True iff the proof is accepted"""
+SKIPPABLE = ("ood", "rem_commit", "query_count", "t_root", "h_root", "deep")
+
+
+def verify(proof, old, new, skip=frozenset()):
+    """winterfell::verify restated for this AIR (stark.rs:190-211): True iff the proof is accepted.
+
+    skip (test infrastructure, tests/stark_forge.py): names from SKIPPABLE of checks that are NOT applied, so that a forgery can be shown
+    to pass a verifier that lacks exactly one check; ("deep", k) leaves out the DEEP identity at the k-th opened position alone."""
+    skip = frozenset(skip)
+    assert all(c in SKIPPABLE or (isinstance(c, tuple) and len(c) == 2 and c[0] == "deep") for c in skip), skip
     try:
         if not (0 <= old < 2**64 and 0 <= new < 2**64):
             return False
@@ -430,27 +438,29 @@ def verify(proof, old, new):
     z = coin.draw()
     coin.reseed(hash_elements([tz, tzg]))
     # out-of-domain consistency: the composition value implied by the trace frame must equal the one sent
-    if constraint_evaluation(z, tz, tzg, old, new, step, coef) != hz:
+    if "ood" not in skip and constraint_evaluation(z, tz, tzg, old, new, step, coef) != hz:
         return False
     coin.reseed(hash_elements([hz]))
     deep = [coin.draw() for _ in range(2)]
-    if hash_elements(remainder) != rem_commit:
+    if "rem_commit" not in skip and hash_elements(remainder) != rem_commit:
         return False
     coin.reseed(rem_commit)
     positions = sorted(set(coin.draw_integers(NUM_QUERIES, LDE_SIZE, 0)))
-    if len(positions) != nq:
+    if "query_count" not in skip and len(positions) != nq:
         return False
     depth = LDE_SIZE.bit_length() - 1
     if t_depth != depth or h_depth != depth:
         return False
-    if batch_root([hash_elements([v]) for v in t_vals], positions, t_nodes, depth) != t_root:
+    if "t_root" not in skip and batch_root([hash_elements([v]) for v in t_vals], positions, t_nodes, depth) != t_root:
         return False
-    if batch_root([hash_elements([v]) for v in h_vals], positions, h_nodes, depth) != h_root:
+    if "h_root" not in skip and batch_root([hash_elements([v]) for v in h_vals], positions, h_nodes, depth) != h_root:
         return False
     # DEEP composition at every query must lie on the committed remainder polynomial (degree < 8; FRI has no layers)
     w = root_of_unity(LDE_SIZE)
     zg = z * g % P
-    for pos, tv, hv in zip(positions, t_vals, h_vals):
+    for k, (pos, tv, hv) in enumerate(zip(positions, t_vals, h_vals)):
+        if "deep" in skip or ("deep", k) in skip:
+            continue
         x = GENERATOR * pow(w, pos, P) % P
         d = (deep[0] * ((tv - tz) * inv(x - z) + (tv - tzg) * inv(x - zg)) + deep[1] * (hv - hz) * inv(x - z)) % P
         if d != horner(remainder, x):
@@ -472,8 +482,8 @@ def prove_improvement(old, new):
     return bytes([2, 5]) + len(payload).to_bytes(4, "little") + (32).to_bytes(4, "little") + payload + commit_improvement(old, new)
 
 
-def verify_improvement(envelope, old):
-    """proof/improvement_proof.rs:37-68"""
+def verify_improvement(envelope, old, skip=frozenset()):
+    """proof/improvement_proof.rs:37-68 (skip: see verify)"""
     b = bytes(envelope)
     if len(b) < 10 or b[0] != 2 or b[1] != 5:
         return False
@@ -484,4 +494,4 @@ def verify_improvement(envelope, old):
     stored_old, new = int.from_bytes(payload[:8], "little"), int.from_bytes(payload[8:16], "little")
     if stored_old != old or new <= old or commitment != commit_improvement(old, new):
         return False
-    return verify(payload[16:], old, new)
+    return verify(payload[16:], old, new, skip)
