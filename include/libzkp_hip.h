@@ -181,11 +181,14 @@ int zkp_hip_prove_equality_batch(uint64_t n, const uint64_t* val1, const uint64_
  * Calls of 4096 jobs and more (a range envelope is two jobs, a threshold envelope one, a consistency envelope of k values k - 1) first
  * try ONE check for all of them: the jobs' folded equations summed under fresh 128-bit weights from getrandom (libzkp_amd/csrc/bpv_impl.inc,
  * kernels k_rlc_*).  Envelopes refused by a framing, commitment, canonicity or identity rule are rejected before that sum and take no part in
- * it; if the sum is the identity every other envelope is accepted, and if it is not the call verifies job by job, so every verdict is the
- * per-job one up to a soundness error of 2^-128 per call.  ZKP_HIP_BATCH_VERIFY_MIN moves the threshold, ZKP_HIP_NO_BATCH_VERIFY=1 removes
- * the check, and ZKP_HIP_BP_BATCH_VERIFY_ONLY=1 (diagnostic) makes a call whose check does not stand fail with ZKP_HIP_E_RUNTIME ("the batch
- * check did not stand") without the job-by-job pass.  All three are read on every call, and hold for the threshold and consistency
- * verifiers below as well. */
+ * it; if the sum is the identity every other envelope is accepted.  If it is not, the same sum is formed per segment of the batch (contiguous
+ * runs of envelopes) from what the check left in device memory, and the call verifies job by job only the segments whose sum is not the
+ * identity -- or the whole batch, when those hold half of its jobs or more (libzkp_hip_bp_localise.h: ZKP_HIP_BP_LOCALISE=0 always verifies
+ * the whole batch job by job, ZKP_HIP_BP_LOCALISE_SEGMENT=<envelopes> sets the segment size, zkp_hip_bp_localise_counters says what calls
+ * did).  Every verdict is the per-job one up to a soundness error of (1 + segments) * 2^-128 per call.  ZKP_HIP_BATCH_VERIFY_MIN moves the
+ * threshold, ZKP_HIP_NO_BATCH_VERIFY=1 removes the check, and ZKP_HIP_BP_BATCH_VERIFY_ONLY=1 (diagnostic) makes a call whose check does not
+ * stand fail with ZKP_HIP_E_RUNTIME ("the batch check did not stand") without segment checks or a job-by-job pass.  All of these are read on
+ * every call, and hold for the threshold and consistency verifiers below as well. */
 int zkp_hip_verify_range_batch(uint64_t n, const uint8_t* proofs, uint64_t stride, const uint32_t* lens,
                                const uint64_t* mins, const uint64_t* maxs, uint8_t* ok);
 /* Same for proof::threshold_proof::verify_threshold(proof, threshold) (threshold_proof.rs:34-47 -> bulletproofs.rs:550-626):

@@ -29,6 +29,8 @@ EXPORTS = (
 )
 # symbols declared in include/libzkp_hip_verify.h (checked by tests/test_abi_verify.py)
 EXPORTS_VERIFY = ("zkp_hip_verify_envelopes", "zkp_hip_verify_envelopes_device")
+# symbols declared in include/libzkp_hip_bp_localise.h (checked by tests/test_abi_bp_localise.py)
+EXPORTS_BP_LOCALISE = ("zkp_hip_bp_localise_counters",)
 
 _lib = None
 
@@ -156,6 +158,9 @@ def lib():
         L.zkp_hip_batch_free.restype = None
         L.zkp_hip_profile_read_kernel.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
         L.zkp_hip_profile_read_kernel.restype = ctypes.c_int
+        if hasattr(L, "zkp_hip_bp_localise_counters"):      # (an older build loaded through ZKP_HIP_LIB has none; api.bp_verify_counters then raises)
+            L.zkp_hip_bp_localise_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
+            L.zkp_hip_bp_localise_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

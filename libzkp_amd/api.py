@@ -541,6 +541,18 @@ def groth16_verify_counters(reset=True):
     return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
 
 
+def bp_verify_counters(reset=True):
+    """What verify_range_batch / verify_threshold_batch / verify_consistency_batch and everything built on them did after batch checks that
+    did not stand, summed over the shards since the last reset (zkp_hip_bp_localise_counters, include/libzkp_hip_bp_localise.h; always
+    counted): {"failed_checks": batch checks (calls or slices) that did not stand, "segment_checks": segments checked by localisation
+    passes, "jobs_again": jobs given the per-job pass after a failed check (the suspects, or the whole batch), "ms": host wall time from the
+    failed checks' verdicts to the calls' returns}.  reset=True zeroes the counters."""
+    ms, failed, segments, jobs = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_bp_localise_counters(ctypes.byref(ms), ctypes.byref(failed), ctypes.byref(segments), ctypes.byref(jobs), 1 if reset else 0),
+                  "zkp_hip_bp_localise_counters")
+    return {"failed_checks": int(failed.value), "segment_checks": int(segments.value), "jobs_again": int(jobs.value), "ms": float(ms.value)}
+
+
 def batch_self_check_counters(reset=True):
     """What the self-check of flagged batches (process_ops / process_batch with self_check=True; ZKP_HIP_OP_SELF_CHECK) did, summed over the
     shards since the last reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_BATCH_SELF_CHECK; always counted): {"launches": ops whose

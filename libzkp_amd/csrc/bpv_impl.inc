@@ -3,14 +3,111 @@
 // the prover's MSM / partial-sum / encode kernels.
 namespace {
 
-struct VfyState { void* buf = nullptr; size_t cap = 0; LayoutSet set; bool ready = false; };      // per shard (Device::vfy)
+struct VfyState { void* buf = nullptr; size_t cap = 0; LayoutSet set; bool ready = false; void* loc_buf = nullptr; size_t loc_cap = 0; };      // per shard (Device::vfy); loc_buf: localise_bp's, created by the first batch check that does not stand
 VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy; }
+
+// What a call did after a batch check that did not stand (zkp_hip_bp_localise_counters): added to the shard's counters when the call
+// returns, whichever way
+struct BpLocaliseTally {
+    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    uint64_t segment_checks = 0, jobs_again = 0;
+    explicit BpLocaliseTally(Device& dv) : d(dv) {}
+    ~BpLocaliseTally() {
+        Device::BpLocaliseCounter& C = d.bp_localise;
+        C.failed_checks++; C.segment_checks += segment_checks; C.jobs_again += jobs_again;
+        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+// After a batch check of V's M jobs (n envelopes) that did not stand (W: the weighted view, Q: the check's point terms): one check per
+// segment says where the bad jobs can be (bp_localise.h), only the suspect segments' jobs get the per-job pass, on compact arrays, and their
+// encodings land in enc among zeros.  *done = false: nothing was decided here and the caller verifies the whole batch (localisation
+// switched off, suspects in half of the batch, or -- against all odds -- no suspect at all).  job_base: the host's copy, or null.
+int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& Q, uint32_t n, uint32_t jobs_per, const uint32_t* job_base, uint32_t* enc,
+                BpLocaliseTally& tally, bool* done) {
+    *done = false;
+    if (env_int("ZKP_HIP_BP_LOCALISE", 1) == 0) return 0;
+    int rc;
+    hipStream_t st = dev().stream;
+    const uint32_t M = V.M;
+    const int forced = env_int("ZKP_HIP_BP_LOCALISE_SEGMENT", 0);
+    const BpSegments g = bp_loc_segments(n, forced > 0 ? (uint32_t)forced : 0u);
+    const uint32_t count = g.count;
+    size_t off = 0;
+    auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
+    auto ensure = [&]() {           // (the buffer only grows; what it held is not needed across a growth)
+        if (off <= S.loc_cap) return 0;
+        if (S.loc_buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(S.loc_buf)); S.loc_buf = nullptr; S.loc_cap = 0; }
+        HIP_TRY(hipMalloc(&S.loc_buf, off)); S.loc_cap = off;
+        return 0;
+    };
+    // ---- the segment checks
+    const DevLayout& Ds = pick_layout(S.set, count);
+    const size_t s_dig = sz((size_t)NBASE * DIGW * 4 * count), s_part = sz((size_t)Ds.nchunks * GE_W * 4 * count), s_gen = sz((size_t)GE_W * 4 * count),
+                 s_win = sz((size_t)count * RLC_NWIN * GE_W * 4), s_sus = sz(count), s_tcb = sz(16);
+    if ((rc = ensure())) return rc;
+    uint8_t* lb = (uint8_t*)S.loc_buf;
+    BpLocView L{}; L.g = g; L.n = n; L.jobs_per = jobs_per; L.job_base = job_base ? V.job_base : nullptr; L.suspect = lb + s_sus; L.off = nullptr;
+    const uint16_t tcbs[2] = {0, (uint16_t)Ds.nchunks};
+    HIP_TRY(hipMemcpyAsync(lb + s_tcb, tcbs, sizeof tcbs, hipMemcpyHostToDevice, st));
+    bpv_launch_seg_fixed_sum(W, L, (uint32_t*)(lb + s_dig), st);
+    if ((rc = launch_msm(Ds, count, (uint32_t*)(lb + s_dig), (uint32_t*)(lb + s_part), st))) return rc;
+    ReduceView Rs; Rs.rows = count; Rs.ntargets = 1; Rs.partial = (uint32_t*)(lb + s_part); Rs.target_chunk_begin = (const uint16_t*)(lb + s_tcb);
+    Rs.enc = nullptr; Rs.out_off = nullptr; Rs.out = nullptr; Rs.corr = nullptr;
+    launch_sum_ed(Rs, (uint32_t*)(lb + s_gen), st);
+    bpv_launch_seg_points(Q, L, M, (uint32_t*)(lb + s_win), (const uint32_t*)(lb + s_gen), lb + s_sus, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> suspect(count);
+    HIP_TRY(hipMemcpyAsync(suspect.data(), lb + s_sus, count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    tally.segment_checks += count;
+    std::vector<uint32_t> offs((size_t)count + 1);
+    const uint32_t Mc = bp_loc_offsets(g, n, jobs_per, job_base, suspect.data(), offs.data());
+    if (Mc == 0 || bp_loc_whole_batch(Mc, M)) return 0;
+    // ---- the per-job pass over the suspects' jobs, compacted
+    const DevLayout& Dc = pick_layout(S.set, Mc);
+    off = 0;
+    const size_t c_sus = sz(count), c_off = sz(4ull * (count + 1)), c_tcb = sz(16),
+                 c_poff = sz(8ull * Mc), c_voff = sz(8ull * Mc), c_kind = sz(Mc), c_lgn = sz(Mc), c_bad = sz(4ull * Mc),
+                 c_pts = sz((size_t)VP_NUM * GE_W * 4 * Mc), c_scal = sz((size_t)VS_NUM * 32 * Mc),
+                 c_zero0 = off, c_dig = sz((size_t)NBASE * DIGW * 4 * Mc), c_vs = sz((size_t)VP_NUM * 32 * Mc), c_zero1 = off,
+                 c_part = sz((size_t)(Dc.nchunks + VP_NUM) * GE_W * 4 * Mc), c_sums = sz((size_t)GE_W * 4 * Mc), c_enc = sz((size_t)32 * Mc);
+    if ((rc = ensure())) return rc;
+    lb = (uint8_t*)S.loc_buf;
+    HIP_TRY(hipMemcpyAsync(lb + c_sus, suspect.data(), count, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(lb + c_off, offs.data(), 4 * offs.size(), hipMemcpyHostToDevice, st));
+    const uint16_t tcbc[2] = {0, (uint16_t)(Dc.nchunks + VP_NUM)};
+    HIP_TRY(hipMemcpyAsync(lb + c_tcb, tcbc, sizeof tcbc, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(lb + c_zero0, 0, c_zero1 - c_zero0, st));
+    L.suspect = lb + c_sus; L.off = (const uint32_t*)(lb + c_off);
+    VfyView C = V;
+    C.M = Mc; C.proof_off = (uint64_t*)(lb + c_poff); C.venc_off = (uint64_t*)(lb + c_voff); C.kind = lb + c_kind; C.lgn = lb + c_lgn; C.bad = (int32_t*)(lb + c_bad);
+    C.pts = (uint32_t*)(lb + c_pts); C.scal = (uint32_t*)(lb + c_scal); C.digits = (uint32_t*)(lb + c_dig); C.vscal = (uint32_t*)(lb + c_vs);
+    C.partial = (uint32_t*)(lb + c_part); C.var_chunk0 = Dc.nchunks; C.rho = nullptr; C.fterm = nullptr;
+    bpv_launch_gather(V, L, C, st);
+    bpv_launch_transcript(C, st);
+    bpv_launch_scalars(C, st);
+    if ((rc = launch_msm(Dc, Mc, C.digits, C.partial, st))) return rc;
+    bpv_launch_varbase(C, st);
+    ReduceView R; R.rows = Mc; R.ntargets = 1; R.partial = C.partial; R.target_chunk_begin = (const uint16_t*)(lb + c_tcb);
+    R.enc = (uint32_t*)(lb + c_enc); R.out_off = nullptr; R.out = nullptr; R.corr = nullptr;
+    uint32_t* sums = (uint32_t*)(lb + c_sums);
+    launch_sum_ed(R, sums, st);
+    k_encode<<<dim3((Mc + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
+    HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * M, st));
+    bpv_launch_scatter(L, R.enc, Mc, enc, M, st);
+    HIP_TRY(hipGetLastError());
+    tally.jobs_again += Mc;
+    *done = true;
+    return 0;
+}
 
 // The verifier on device pointers: n envelopes at `stride` bytes in d_proofs, d_lens[i] bytes used, verdicts into d_ok (device); waits for them.
 // scheme: ZKP_HIP_OP_RANGE (bounds = d_mins, d_maxs; two jobs per envelope), ZKP_HIP_OP_THRESHOLD (bounds = thresholds, d_maxs unused; one job)
 // or ZKP_HIP_OP_CONSISTENCY (no bounds; job_counts[i] jobs for envelope i, a host array from the caller -- the host entry point counts k - 1
 // from each envelope's own k field, the batch self-check knows its ops' list lengths; the device step rejects an envelope whose k disagrees).
-// The batch check (k_rlc_*), its fallback and its three switches are in here, so every caller gets the same verdicts.
+// The batch check (k_rlc_*), what follows one that does not stand (localise_bp, or the per-job pass over everything) and their switches
+// are in here, so every caller gets the same verdicts.
 // ok_host (may be null): the verdicts are also copied there before the one wait that ends the call.
 int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t stride, const uint32_t* d_lens, const uint64_t* d_mins, const uint64_t* d_maxs, uint8_t* d_ok,
                      const uint32_t* job_counts, uint8_t* ok_host) {
@@ -72,12 +169,13 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
     else if (scheme == ZKP_HIP_OP_THRESHOLD) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_lens, d_mins, st);
     else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_lens, st);
     uint32_t* enc = (uint32_t*)(base + o_enc);
-    bool accepted_as_a_batch = false;
+    bool accepted_as_a_batch = false, located = false;      // located: the check did not stand and localise_bp has put the suspects' encodings into enc
+    std::unique_ptr<BpLocaliseTally> tally;                  // set once the batch check has not stood
     if (M) bpv_launch_decode(V, st);
     if (M && batch_mode) {
         // One check for the whole batch: sum_j rho_j (job j's combination) == 0 with fresh 128-bit weights from the OS, as
         // upstream's batch verification does.  It passes iff every job that survived parsing / decoding verifies (up to 2^-128);
-        // if it fails, the per-job path below says which envelopes are the bad ones.
+        // if it fails, segment checks (localise_bp) say where the bad envelopes can be and the per-job path says which they are.
         std::vector<uint8_t> rnd; if ((rc = fresh_seeds(rnd, (M + 1) / 2))) return rc;               // 16 bytes per job
         std::vector<uint32_t> rho((size_t)8 * M);
         for (uint32_t j = 0; j < M; j++) {
@@ -114,9 +212,16 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
         if (!accepted_as_a_batch && getenv("ZKP_HIP_BP_BATCH_VERIFY_ONLY"))                           // diagnostic: the verdict of this check, no per-job pass
             return fail(ZKP_HIP_E_RUNTIME, "Bulletproofs verification: the batch check did not stand and ZKP_HIP_BP_BATCH_VERIFY_ONLY is set");
         if (accepted_as_a_batch) HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * Mw, st));                // every surviving job's sum is the identity
-        else HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));                     // weighted scalars out, per-job path below
+        else {
+            tally.reset(new BpLocaliseTally(dev()));
+            if ((rc = localise_bp(S, V, W, Q, (uint32_t)n, jobs_per, consistency ? job_base.data() : nullptr, enc, *tally, &located))) return rc;
+            if (!located) {
+                tally->jobs_again += M;
+                HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));                  // weighted scalars out, per-job path below
+            }
+        }
     }
-    if (M && !accepted_as_a_batch) {
+    if (M && !accepted_as_a_batch && !located) {
         bpv_launch_transcript(V, st);
         bpv_launch_scalars(V, st);
         if ((rc = launch_msm(D, M, V.digits, V.partial, st))) return rc;
@@ -169,6 +274,7 @@ int verify_bp_call(int scheme, uint64_t n, const uint8_t* proofs, uint64_t strid
 void bpv_release_all() {
     if (!dev().vfy) return;
     if (dev().vfy->buf) (void)hipFree(dev().vfy->buf);
+    if (dev().vfy->loc_buf) (void)hipFree(dev().vfy->loc_buf);
     free_set(dev().vfy->set);
     delete dev().vfy; dev().vfy = nullptr;
 }
@@ -193,6 +299,24 @@ int zkp_hip_verify_consistency_batch(uint64_t n, const uint8_t* proofs, uint64_t
     if (n == 0) return 0;
     const int rc = verifier_args(n, {proofs, lens, ok}, stride);
     return rc ? rc : verify_bp_call(ZKP_HIP_OP_CONSISTENCY, n, proofs, stride, lens, nullptr, nullptr, ok);
+} ZKP_API_CATCH_INT
+
+// accumulated over all shards (BpLocaliseTally); needs no device
+int zkp_hip_bp_localise_counters(double* ms, uint64_t* failed_checks, uint64_t* segment_checks, uint64_t* jobs_again, int reset) try {
+    std::vector<Device*> shards;
+    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
+    Device::BpLocaliseCounter T;
+    for (Device* d : shards) {
+        std::lock_guard<std::mutex> dl(d->mu);
+        Device::BpLocaliseCounter& C = d->bp_localise;
+        T.ms += C.ms; T.failed_checks += C.failed_checks; T.segment_checks += C.segment_checks; T.jobs_again += C.jobs_again;
+        if (reset) C = Device::BpLocaliseCounter();
+    }
+    if (ms) *ms = T.ms;
+    if (failed_checks) *failed_checks = T.failed_checks;
+    if (segment_checks) *segment_checks = T.segment_checks;
+    if (jobs_again) *jobs_again = T.jobs_again;
+    return 0;
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

@@ -156,17 +156,25 @@ __device__ __forceinline__ fe fe_readlane(const fe& x, int lane) {
     fe r; ZKP_UNROLL for (int k = 0; k < 10; k++) r.v[k] = (uint32_t)__builtin_amdgcn_readlane((int)x.v[k], lane);
     return r;
 }
-__device__ __forceinline__ ge ge_dbl_lanes(const ge& p, uint32_t role) {
+// where the four lanes are: lanes 0..3 of the wave (k_rlc_final), or the lane's own quad (k_bp_seg_close: sixteen chains per wave, a DPP move each)
+struct LanesOfWave { template <int R> static __device__ __forceinline__ fe get(const fe& x) { return fe_readlane(x, R); } };
+struct LanesOfQuad {
+    template <int R> static __device__ __forceinline__ fe get(const fe& x) {
+        fe r; ZKP_UNROLL for (int k = 0; k < 10; k++) r.v[k] = (uint32_t)__builtin_amdgcn_mov_dpp((int)x.v[k], R * 0x55, 0xf, 0xf, true);      // quad_perm: [R, R, R, R]
+        return r;
+    }
+};
+template <class G> __device__ __forceinline__ ge ge_dbl_lanes(const ge& p, uint32_t role) {
     const fe xy = fe_add(p.X, p.Y);
     const fe in = fe_select(role == 0, p.X, fe_select(role == 1, p.Y, fe_select(role == 2, p.Z, xy)));
     const fe s = fe_sq(in);
-    const fe A = fe_readlane(s, 0), B = fe_readlane(s, 1), zz = fe_readlane(s, 2), t = fe_readlane(s, 3);
+    const fe A = G::template get<0>(s), B = G::template get<1>(s), zz = G::template get<2>(s), t = G::template get<3>(s);
     const fe C = fe_add(zz, zz);
     const fe Hn = fe_add(A, B), En = fe_sub(Hn, t), Gn = fe_sub(A, B), Fn = fe_carry(fe_add(C, Gn));      // as ge_dbl
     const fe a = fe_select(role == 1, Gn, fe_select(role == 2, Fn, En));                                  // En*Fn, Gn*Hn, Fn*Gn, En*Hn
     const fe b = fe_select(role == 0, Fn, fe_select(role == 2, Gn, Hn));
     const fe m = fe_mul(a, b);
-    ge r; r.X = fe_readlane(m, 0); r.Y = fe_readlane(m, 1); r.Z = fe_readlane(m, 2); r.T = fe_readlane(m, 3);
+    ge r; r.X = G::template get<0>(m); r.Y = G::template get<1>(m); r.Z = G::template get<2>(m); r.T = G::template get<3>(m);
     return r;
 }
 // one block: eight lanes per window join its segment sums, then wave 0 runs the Horner chain over the windows
@@ -188,7 +196,7 @@ __global__ void __launch_bounds__(RLC_FINAL_T) k_rlc_final(RlcView R) {
     const uint32_t role = t & 3u;
     ge acc = ld_ge_flat(lds, RLC_NWIN - 1);
     for (int k = (int)RLC_NWIN - 2; k >= 0; k--) {
-        for (uint32_t d = 0; d < RLC_WBITS; d++) acc = ge_dbl_lanes(acc, role);
+        for (uint32_t d = 0; d < RLC_WBITS; d++) acc = ge_dbl_lanes<LanesOfWave>(acc, role);
         acc = ge_add(acc, ld_ge_flat(lds, k));
     }
     if (t != 0) return;
@@ -211,6 +219,100 @@ __global__ void __launch_bounds__(VTB) k_rlc_fixed_sum(VfyView V, uint32_t* digi
     }
     if (t == 0) st_digits(digits1, g, 0, 1, acc, V.wbits);
 }
+
+// ================================================================================================ localisation (bp_localise.h)
+// After a batch check that did not stand: the same sum per segment of envelopes, from the Niels rows, digits and weighted generator
+// coefficients the check left behind.
+// thread = (generator, segment): sum of the segment's jobs' weighted coefficients -> row s of the S-row fixed-base MSM
+__global__ void __launch_bounds__(VTW) k_bp_seg_fixed_sum(VfyView V, BpLocView L, uint32_t* digits) {
+    const uint32_t g = blockIdx.x, s = blockIdx.y * VTW + threadIdx.x;
+    if (s >= L.g.count) return;
+    sc acc = sc_zero();
+    for (uint32_t j = bp_loc_job_lo(L.g, s, L.jobs_per, L.job_base), hi = bp_loc_job_hi(L.g, L.n, s, L.jobs_per, L.job_base); j < hi; j++) acc = sc_add(acc, ld_sc(V.fterm, g, j, V.M));
+    st_digits(digits, g, s, L.g.count, acc, V.wbits);
+}
+__device__ __forceinline__ ge ge_shfl_down(const ge& g, uint32_t delta) {
+    ge r;
+    ZKP_UNROLL for (int k = 0; k < 10; k++) {
+        r.X.v[k] = __shfl_down(g.X.v[k], delta); r.Y.v[k] = __shfl_down(g.Y.v[k], delta); r.Z.v[k] = __shfl_down(g.Z.v[k], delta); r.T.v[k] = __shfl_down(g.T.v[k], delta);
+    }
+    return r;
+}
+__device__ __forceinline__ ge ge_select(bool c, const ge& a, const ge& b) {
+    ge r; r.X = fe_select(c, a.X, b.X); r.Y = fe_select(c, a.Y, b.Y); r.Z = fe_select(c, a.Z, b.Z); r.T = fe_select(c, a.T, b.T);
+    return r;
+}
+// one wave = (segment, window): the steps of bp_localise.h tile by tile, then sum_b b B_b in each half of the wave as the sum of the
+// suffix sums (five shuffle steps for the suffix sums, five for their sum), and 32 H + L.  win = [S][NWIN][40]
+static_assert(VTW == BP_LOC_LANES, "one wave per (segment, window)");
+__global__ void __launch_bounds__(VTW) k_bp_seg_points(RlcView R, BpLocView L, uint32_t M, uint32_t* win) {
+    __shared__ BpLocTile T;
+    const uint32_t s = blockIdx.x, w = blockIdx.y, t = threadIdx.x, q = t & 31u;
+    const uint32_t lo = bp_loc_job_lo(L.g, s, L.jobs_per, L.job_base), hi = bp_loc_job_hi(L.g, L.n, s, L.jobs_per, L.job_base);      // the same in every lane: the barriers below are uniform
+    ge acc = ge_identity();
+    for (uint32_t j0 = lo; j0 < hi; j0 += BP_LOC_TILE_JOBS) {
+        const uint32_t nj = hi - j0 < BP_LOC_TILE_JOBS ? hi - j0 : BP_LOC_TILE_JOBS;
+        T.cursor[t] = 0;
+        __syncthreads();
+        bp_loc_step_sort(T, R, M, w, j0, nj, t, false);
+        __syncthreads();
+        if (t == 0) bp_loc_step_scan(T);
+        __syncthreads();
+        bp_loc_step_sort(T, R, M, w, j0, nj, t, true);
+        __syncthreads();
+        acc = bp_loc_step_walk(acc, T, R, M, j0, nj, t);
+        __syncthreads();
+    }
+    for (uint32_t d = 1; d < 32; d <<= 1) acc = ge_add(acc, ge_select(q + d < 32, ge_shfl_down(acc, d), ge_identity()));      // lane b: sum of the lanes b .. 31 of its half
+    if (t == 0) acc = ge_identity();                                                                                          // l = 0 is no bucket
+    for (int m = 16; m >= 1; m >>= 1) acc = ge_add(acc, ge_shfl_xor(acc, m));
+    ge r = ge_shfl_xor(acc, 32);                                       // lane 0: H
+    for (int k = 0; k < 5; k++) r = ge_dbl(r);
+    if (t == 0) st_ge_flat(win, (size_t)s * RLC_NWIN + w, ge_add(r, acc));
+}
+// four lanes = segment: Horner over the windows, the segment's generator point (gen = [40][S], launch_sum_ed), the ristretto encoding
+constexpr uint32_t BP_LOC_CLOSE_SEGS = VTW / 4;
+__global__ void __launch_bounds__(VTW) k_bp_seg_close(BpLocView L, const uint32_t* win, const uint32_t* gen, uint8_t* suspect) {
+    const uint32_t s = blockIdx.x * BP_LOC_CLOSE_SEGS + (threadIdx.x >> 2), role = threadIdx.x & 3u;
+    const uint32_t sv = s < L.g.count ? s : L.g.count - 1;            // lanes past the last segment repeat it, so every quad is whole
+    ge acc = ld_ge_flat(win, (size_t)sv * RLC_NWIN + RLC_NWIN - 1);
+    for (int k = (int)RLC_NWIN - 2; k >= 0; k--) {
+        for (uint32_t d = 0; d < RLC_WBITS; d++) acc = ge_dbl_lanes<LanesOfQuad>(acc, role);
+        acc = ge_add(acc, ld_ge_flat(win, (size_t)sv * RLC_NWIN + k));
+    }
+    acc = ge_add(acc, ld_ge(gen, 0, sv, L.g.count));
+    uint32_t e[8]; ge_ristretto_encode(e, acc);
+    if (s < L.g.count && role == 0) suspect[s] = words_are_zero(e) ? 0 : 1;      // (a segment without a live job sums to the identity)
+}
+// block = suspect segment: its jobs' rows into the compact arrays C (C.M jobs) / their encodings back into the batch's
+__global__ void __launch_bounds__(VTB) k_bp_gather(VfyView V, BpLocView L, VfyView C) {
+    const uint32_t s = blockIdx.x;
+    if (!L.suspect[s]) return;
+    const uint32_t lo = bp_loc_job_lo(L.g, s, L.jobs_per, L.job_base), hi = bp_loc_job_hi(L.g, L.n, s, L.jobs_per, L.job_base);
+    for (uint32_t j = lo + threadIdx.x; j < hi; j += VTB) {
+        const uint32_t c = bp_loc_compact_index(L.off, s, lo, j);
+        C.proof_off[c] = V.proof_off[j]; C.venc_off[c] = V.venc_off[j]; C.kind[c] = V.kind[j]; C.lgn[c] = V.lgn[j]; C.bad[c] = V.bad[j];
+        if (V.bad[j]) continue;
+        for (uint32_t k = 0; k < VP_NUM * GE_W; k++) C.pts[(size_t)k * C.M + c] = V.pts[(size_t)k * V.M + j];
+    }
+}
+__global__ void __launch_bounds__(VTB) k_bp_scatter(BpLocView L, const uint32_t* cenc, uint32_t Mc, uint32_t* enc, uint32_t M) {
+    const uint32_t s = blockIdx.x;
+    if (!L.suspect[s]) return;
+    const uint32_t lo = bp_loc_job_lo(L.g, s, L.jobs_per, L.job_base), hi = bp_loc_job_hi(L.g, L.n, s, L.jobs_per, L.job_base);
+    for (uint32_t j = lo + threadIdx.x; j < hi; j += VTB) {
+        const uint32_t c = bp_loc_compact_index(L.off, s, lo, j);
+        for (uint32_t k = 0; k < 8; k++) enc[(size_t)k * M + j] = cenc[(size_t)k * Mc + c];
+    }
+}
+void bpv_launch_seg_fixed_sum(const VfyView& V, const BpLocView& L, uint32_t* d_digits, hipStream_t st) { k_bp_seg_fixed_sum<<<dim3(NBASE, (L.g.count + VTW - 1) / VTW), VTW, 0, st>>>(V, L, d_digits); }
+void bpv_launch_seg_points(const RlcView& R, const BpLocView& L, uint32_t M, uint32_t* d_win, const uint32_t* d_gen, uint8_t* d_suspect, hipStream_t st) {
+    k_bp_seg_points<<<dim3(L.g.count, RLC_NWIN), VTW, 0, st>>>(R, L, M, d_win);
+    k_bp_seg_close<<<(L.g.count + BP_LOC_CLOSE_SEGS - 1) / BP_LOC_CLOSE_SEGS, VTW, 0, st>>>(L, d_win, d_gen, d_suspect);
+}
+void bpv_launch_gather(const VfyView& V, const BpLocView& L, const VfyView& C, hipStream_t st) { k_bp_gather<<<L.g.count, VTB, 0, st>>>(V, L, C); }
+void bpv_launch_scatter(const BpLocView& L, const uint32_t* d_cenc, uint32_t Mc, uint32_t* d_enc, uint32_t M, hipStream_t st) { k_bp_scatter<<<L.g.count, VTB, 0, st>>>(L, d_cenc, Mc, d_enc, M); }
+
 void bpv_launch_rlc_points(const VfyView& V, const RlcView& R, hipStream_t st) { k_rlc_points<<<dim3((V.M + VTB - 1) / VTB, VP_NUM), VTB, 0, st>>>(V, R); }
 void bpv_launch_rlc_sort(const RlcView& R, hipStream_t st) {
     k_rlc_scan<<<RLC_NWIN, RLC_NBUCKET, 0, st>>>(R);

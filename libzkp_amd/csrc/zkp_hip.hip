@@ -41,6 +41,7 @@
 #include "verify_shards.h"
 #include "venv_steps.h"
 #include "../../include/libzkp_hip_verify.h"
+#include "../../include/libzkp_hip_bp_localise.h"
 
 // ================================================================================================ kernels
 
@@ -352,6 +353,8 @@ struct Device {
     struct HostCounter { double ms = 0; uint64_t a = 0, b = 0; };
     HostCounter host[ZKP_HIP_COUNTER_VERIFY_MIXED - ZKP_HIP_COUNTER_G16_VERIFY + 1];
     HostCounter& counter(int which) { return host[which - ZKP_HIP_COUNTER_G16_VERIFY]; }
+    // zkp_hip_bp_localise_counters (libzkp_hip_bp_localise.h): what the Bulletproofs verifiers did after batch checks that did not stand (BpLocaliseTally)
+    struct BpLocaliseCounter { double ms = 0; uint64_t failed_checks = 0, segment_checks = 0, jobs_again = 0; } bp_localise;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -1240,6 +1243,7 @@ void zkp_hip_shutdown(void) try {
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
         for (auto& C : d->host) C = Device::HostCounter();
+        d->bp_localise = Device::BpLocaliseCounter();
         d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
