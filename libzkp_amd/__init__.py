@@ -20,6 +20,7 @@ from .batch_store import set_batch_store_dir, get_batch_store_dir, list_batch_id
 from .composite import (  # noqa: F401
     create_composite_proof, verify_composite_proof, verify_composite_proof_integrity_only, create_proof_with_metadata,
     extract_proof_metadata, verify_proofs_parallel, validate_proof_chain, get_proof_info,
+    verify_composite_proofs, verify_composites_counters,
 )
 from ._native import NativeError  # noqa: F401
 from .api import generator_table_info, groth16_verify_counters, batch_self_check_counters, verify_fanout_counters, verify_envelopes, verify_mixed_counters, bp_verify_counters  # noqa: F401  (extensions of this backend, not among the reference's names above)
@@ -39,5 +40,6 @@ __all__ = [
     "set_batch_store_dir", "get_batch_store_dir", "list_batch_ids_in_store",
     "NativeError", "ZkpBackendError", "shutdown",
     "generator_table_info", "groth16_verify_counters", "batch_self_check_counters", "verify_fanout_counters", "verify_envelopes", "verify_mixed_counters", "bp_verify_counters",
+    "verify_composite_proofs", "verify_composites_counters",
     "clear_cache", "get_cache_stats", "get_performance_metrics", "prove_range_cached", "prove_threshold_optimized",
 ]

@@ -31,6 +31,9 @@ EXPORTS = (
 EXPORTS_VERIFY = ("zkp_hip_verify_envelopes", "zkp_hip_verify_envelopes_device")
 # symbols declared in include/libzkp_hip_bp_localise.h (checked by tests/test_abi_bp_localise.py)
 EXPORTS_BP_LOCALISE = ("zkp_hip_bp_localise_counters",)
+# symbols declared in include/libzkp_hip_composites.h (checked by tests/test_abi_composites.py)
+EXPORTS_COMPOSITES = ("zkp_hip_verify_composites", "zkp_hip_composites_counters")
+COMPOSITES_INTEGRITY_ONLY = 1     # ZKP_HIP_COMPOSITES_INTEGRITY_ONLY: digests only
 
 _lib = None
 
@@ -161,6 +164,11 @@ def lib():
         if hasattr(L, "zkp_hip_bp_localise_counters"):      # (an older build loaded through ZKP_HIP_LIB has none; api.bp_verify_counters then raises)
             L.zkp_hip_bp_localise_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
             L.zkp_hip_bp_localise_counters.restype = ctypes.c_int
+        if hasattr(L, "zkp_hip_verify_composites"):         # (an older build loaded through ZKP_HIP_LIB has none; composite.verify_composite_proofs then raises)
+            L.zkp_hip_verify_composites.argtypes = [u64, vp, vp, u32, vp]
+            L.zkp_hip_verify_composites.restype = ctypes.c_int
+            L.zkp_hip_composites_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
+            L.zkp_hip_composites_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

@@ -148,6 +148,80 @@ def verify_composite_proof(composite_bytes):
     return all(verify_proof_cryptographic_batch(proofs))
 
 
+def _groth16_circuits_in(blob):
+    """Which Groth16 circuits (0: equality, 1: membership) the inner envelopes of a container name, from a walk over the proof length
+    prefixes alone; a container the walk cannot follow names none (the library decides whether it is malformed)."""
+    kinds = set()
+    if len(blob) < 12 or blob[:4] != b"COMP":
+        return kinds
+    nproofs, off = int.from_bytes(blob[4:8], "little"), 12
+    for _ in range(min(nproofs, 1000)):
+        if off + 6 > len(blob):
+            break
+        if blob[off + 5] == 2:
+            kinds.add(0)
+        elif blob[off + 5] == 4:
+            kinds.add(1)
+        off += 4 + int.from_bytes(blob[off:off + 4], "little")
+    return kinds
+
+
+def verify_composite_proofs(composites, integrity_only=False, errors="false"):
+    """verify_composite_proof (or, with integrity_only, verify_composite_proof_integrity_only) for a list of containers in ONE library call
+    (zkp_hip_verify_composites, include/libzkp_hip_composites.h): the digests are computed on the GPU, all inner envelopes of all
+    well-formed containers go through one pass of the mixed verifier, and the verdicts come back per container as a list of bools.
+    errors="false": a malformed container is False.  errors="raise": the first malformed container is parsed again with parse_composite,
+    which raises the reference's ProofFormatError for it."""
+    import ctypes
+    import numpy as np
+    from . import _native, api
+    if errors not in ("false", "raise"):
+        raise ValueError("errors must be 'false' or 'raise'")
+    blobs = [bytes(c) for c in composites]
+    n = len(blobs)
+    if n == 0:
+        return []
+    if not integrity_only:                                # a Groth16 key only for the circuits whose scheme byte occurs
+        needed = set()
+        for b in blobs:
+            needed |= _groth16_circuits_in(b)
+            if len(needed) == 2:
+                break
+        for kind in sorted(needed):
+            api._ensure_key(kind, verifier=True)
+    L = _native.lib()
+    if not hasattr(L, "zkp_hip_verify_composites"):
+        raise _native.NativeError("this build of libzkp_hip.so has no zkp_hip_verify_composites")
+    blob = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(b) for b in blobs), dtype=np.uint64, count=n), out=off[1:])
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    status = np.zeros(n, dtype=np.uint8)
+    vp = ctypes.c_void_p
+    _native.check(L.zkp_hip_verify_composites(n, blob.ctypes.data_as(vp), off.ctypes.data_as(vp), _native.COMPOSITES_INTEGRITY_ONLY if integrity_only else 0,
+                                              status.ctypes.data_as(vp)), "zkp_hip_verify_composites")
+    if errors == "raise":
+        malformed = np.flatnonzero(status == 2)
+        if malformed.size:
+            parse_composite(blobs[int(malformed[0])])
+            raise ProofFormatError("Invalid proof format: composite proof %d is malformed" % int(malformed[0]))      # (not reached while the library and parse_composite agree)
+    return (status == 1).tolist()
+
+
+def verify_composites_counters(reset=True):
+    """What verify_composite_proofs did, summed over the shards since the last reset (zkp_hip_composites_counters,
+    include/libzkp_hip_composites.h; always counted): {"composites": containers seen, "malformed": containers that
+    CompositeProof::from_bytes refuses, "envelopes": inner envelopes handed to the mixed verifier, "ms": host wall time of the calls}.
+    reset=True zeroes the counters."""
+    import ctypes
+    from . import _native
+    ms, composites, malformed, envelopes = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkp_hip_composites_counters(ctypes.byref(ms), ctypes.byref(composites), ctypes.byref(malformed), ctypes.byref(envelopes), 1 if reset else 0),
+                  "zkp_hip_composites_counters")
+    return {"composites": int(composites.value), "malformed": int(malformed.value), "envelopes": int(envelopes.value), "ms": float(ms.value)}
+
+
 def verify_proofs_parallel(proofs):
     """[(proof bytes, type name)] -> [bool]: the type must match the envelope's scheme id (performance.rs:269-293)."""
     from . import api
