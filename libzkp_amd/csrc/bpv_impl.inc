@@ -1,10 +1,46 @@
 // Range, threshold and consistency verification, host side of libzkp_hip (included by zkp_hip.hip): the core on device pointers
-// (verify_bp_device), one slice of a host-buffer call (verify_bp_host) and the three entry points on verify_call.  Kernels: bpv_kernels.hip +
-// the prover's MSM / partial-sum / encode kernels.
+// (verify_bp_device) with what follows a batch check that does not stand (localise_bp), both on the workspace plan of bpv_plan.h and on one
+// per-job pass (per_job_pass) and one fixed-base sum (fixed_base_sum); one slice of a host-buffer call (verify_bp_host), the three entry
+// points on verify_call and the localisation counters.  Kernels: bpv_kernels.hip + the prover's MSM / partial-sum / encode kernels.
+#include "bpv_plan.h"
 namespace {
 
-struct VfyState { void* buf = nullptr; size_t cap = 0; LayoutSet set; bool ready = false; void* loc_buf = nullptr; size_t loc_cap = 0; };      // per shard (Device::vfy); loc_buf: localise_bp's, created by the first batch check that does not stand
+// A device buffer that only grows.  What it held is not needed across a growth; the device is idle before the old block is freed.
+struct GrowBuf {
+    uint8_t* p = nullptr; size_t cap = 0;
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        if (p) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
+        HIP_TRY(hipMalloc(&p, bytes)); cap = bytes;
+        return 0;
+    }
+};
+struct VfyState { GrowBuf buf, loc; LayoutSet set; bool ready = false; };      // per shard (Device::vfy); buf: the batch block, loc: localise_bp's two shapes (bpv_plan.h), created by the first batch check that does not stand
 VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy; }
+
+// The per-job pass over the C.M jobs of a view bound to the job arrays J at `base` (D: the layout J was planned for; digits and vscal zeroed,
+// J.chunk_table at J.tcb): every job's folded equation as one multiscalar sum -- the generator terms through the fixed-base MSM, the proof
+// points one lane each -- and its ristretto encoding into the block's enc rows, 32 zero bytes iff the job verifies
+int per_job_pass(const VfyView& C, const DevLayout& D, uint8_t* base, const BpvJobArrays& J, hipStream_t st) {
+    bpv_launch_transcript(C, st);
+    bpv_launch_scalars(C, st);
+    if (int rc = launch_msm(D, C.M, C.digits, C.partial, st)) return rc;
+    bpv_launch_varbase(C, st);
+    ReduceView R{}; R.rows = C.M; R.ntargets = 1; R.partial = C.partial; R.target_chunk_begin = (const uint16_t*)(base + J.tcb); R.enc = (uint32_t*)(base + J.enc);
+    uint32_t* sums = (uint32_t*)(base + J.sums);
+    launch_sum_ed(R, sums, st);
+    k_encode<<<dim3((C.M + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
+    return 0;
+}
+// sums[r] = the generators' sum under row r of `rows` rows of fixed-base digits: the MSM's chunk partials, summed over D's own chunk table
+// (targets_verify is one target: {0, nchunks}, as the prover's launch_reduce reads it)
+int fixed_base_sum(const DevLayout& D, uint32_t rows, const uint32_t* digits, uint32_t* partial, uint32_t* sums, hipStream_t st) {
+    if (D.ntargets != 1) return fail(ZKP_HIP_E_RUNTIME, "Bulletproofs verification: the generator layout has more than one target");
+    if (int rc = launch_msm(D, rows, digits, partial, st)) return rc;
+    ReduceView R{}; R.rows = rows; R.ntargets = 1; R.partial = partial; R.target_chunk_begin = D.target_chunk_begin;
+    launch_sum_ed(R, sums, st);
+    return 0;
+}
 
 // What a call did after a batch check that did not stand (zkp_hip_bp_localise_counters): added to the shard's counters when the call
 // returns, whichever way
@@ -33,32 +69,18 @@ int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& 
     const int forced = env_int("ZKP_HIP_BP_LOCALISE_SEGMENT", 0);
     const BpSegments g = bp_loc_segments(n, forced > 0 ? (uint32_t)forced : 0u);
     const uint32_t count = g.count;
-    size_t off = 0;
-    auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    auto ensure = [&]() {           // (the buffer only grows; what it held is not needed across a growth)
-        if (off <= S.loc_cap) return 0;
-        if (S.loc_buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(S.loc_buf)); S.loc_buf = nullptr; S.loc_cap = 0; }
-        HIP_TRY(hipMalloc(&S.loc_buf, off)); S.loc_cap = off;
-        return 0;
-    };
     // ---- the segment checks
     const DevLayout& Ds = pick_layout(S.set, count);
-    const size_t s_dig = sz((size_t)NBASE * DIGW * 4 * count), s_part = sz((size_t)Ds.nchunks * GE_W * 4 * count), s_gen = sz((size_t)GE_W * 4 * count),
-                 s_win = sz((size_t)count * RLC_NWIN * GE_W * 4), s_sus = sz(count), s_tcb = sz(16);
-    if ((rc = ensure())) return rc;
-    uint8_t* lb = (uint8_t*)S.loc_buf;
-    BpLocView L{}; L.g = g; L.n = n; L.jobs_per = jobs_per; L.job_base = job_base ? V.job_base : nullptr; L.suspect = lb + s_sus; L.off = nullptr;
-    const uint16_t tcbs[2] = {0, (uint16_t)Ds.nchunks};
-    HIP_TRY(hipMemcpyAsync(lb + s_tcb, tcbs, sizeof tcbs, hipMemcpyHostToDevice, st));
-    bpv_launch_seg_fixed_sum(W, L, (uint32_t*)(lb + s_dig), st);
-    if ((rc = launch_msm(Ds, count, (uint32_t*)(lb + s_dig), (uint32_t*)(lb + s_part), st))) return rc;
-    ReduceView Rs; Rs.rows = count; Rs.ntargets = 1; Rs.partial = (uint32_t*)(lb + s_part); Rs.target_chunk_begin = (const uint16_t*)(lb + s_tcb);
-    Rs.enc = nullptr; Rs.out_off = nullptr; Rs.out = nullptr; Rs.corr = nullptr;
-    launch_sum_ed(Rs, (uint32_t*)(lb + s_gen), st);
-    bpv_launch_seg_points(Q, L, M, (uint32_t*)(lb + s_win), (const uint32_t*)(lb + s_gen), lb + s_sus, st);
+    const BpvSegmentPlan Ps = bpv_plan_segments(count, Ds.nchunks);
+    uint8_t*& lb = S.loc.p;                                         // the block in use: another one after a growth
+    if ((rc = S.loc.reserve(Ps.total))) return rc;
+    BpLocView L{}; L.g = g; L.n = n; L.jobs_per = jobs_per; L.job_base = job_base ? V.job_base : nullptr; L.suspect = lb + Ps.suspect; L.off = nullptr;
+    bpv_launch_seg_fixed_sum(W, L, (uint32_t*)(lb + Ps.dig), st);
+    if ((rc = fixed_base_sum(Ds, count, (uint32_t*)(lb + Ps.dig), (uint32_t*)(lb + Ps.part), (uint32_t*)(lb + Ps.gen), st))) return rc;
+    bpv_launch_seg_points(Q, L, M, (uint32_t*)(lb + Ps.win), (const uint32_t*)(lb + Ps.gen), lb + Ps.suspect, st);
     HIP_TRY(hipGetLastError());
     std::vector<uint8_t> suspect(count);
-    HIP_TRY(hipMemcpyAsync(suspect.data(), lb + s_sus, count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(suspect.data(), lb + Ps.suspect, count, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     tally.segment_checks += count;
     std::vector<uint32_t> offs((size_t)count + 1);
@@ -66,36 +88,19 @@ int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& 
     if (Mc == 0 || bp_loc_whole_batch(Mc, M)) return 0;
     // ---- the per-job pass over the suspects' jobs, compacted
     const DevLayout& Dc = pick_layout(S.set, Mc);
-    off = 0;
-    const size_t c_sus = sz(count), c_off = sz(4ull * (count + 1)), c_tcb = sz(16),
-                 c_poff = sz(8ull * Mc), c_voff = sz(8ull * Mc), c_kind = sz(Mc), c_lgn = sz(Mc), c_bad = sz(4ull * Mc),
-                 c_pts = sz((size_t)VP_NUM * GE_W * 4 * Mc), c_scal = sz((size_t)VS_NUM * 32 * Mc),
-                 c_zero0 = off, c_dig = sz((size_t)NBASE * DIGW * 4 * Mc), c_vs = sz((size_t)VP_NUM * 32 * Mc), c_zero1 = off,
-                 c_part = sz((size_t)(Dc.nchunks + VP_NUM) * GE_W * 4 * Mc), c_sums = sz((size_t)GE_W * 4 * Mc), c_enc = sz((size_t)32 * Mc);
-    if ((rc = ensure())) return rc;
-    lb = (uint8_t*)S.loc_buf;
-    HIP_TRY(hipMemcpyAsync(lb + c_sus, suspect.data(), count, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(lb + c_off, offs.data(), 4 * offs.size(), hipMemcpyHostToDevice, st));
-    const uint16_t tcbc[2] = {0, (uint16_t)(Dc.nchunks + VP_NUM)};
-    HIP_TRY(hipMemcpyAsync(lb + c_tcb, tcbc, sizeof tcbc, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(lb + c_zero0, 0, c_zero1 - c_zero0, st));
-    L.suspect = lb + c_sus; L.off = (const uint32_t*)(lb + c_off);
-    VfyView C = V;
-    C.M = Mc; C.proof_off = (uint64_t*)(lb + c_poff); C.venc_off = (uint64_t*)(lb + c_voff); C.kind = lb + c_kind; C.lgn = lb + c_lgn; C.bad = (int32_t*)(lb + c_bad);
-    C.pts = (uint32_t*)(lb + c_pts); C.scal = (uint32_t*)(lb + c_scal); C.digits = (uint32_t*)(lb + c_dig); C.vscal = (uint32_t*)(lb + c_vs);
-    C.partial = (uint32_t*)(lb + c_part); C.var_chunk0 = Dc.nchunks; C.rho = nullptr; C.fterm = nullptr;
+    const BpvCompactPlan Pc = bpv_plan_compact(count, Mc, Dc.nchunks);
+    if ((rc = S.loc.reserve(Pc.total))) return rc;                 // (maybe a new block, and the second shape in either case: the suspect bytes go up again)
+    HIP_TRY(hipMemcpyAsync(lb + Pc.suspect, suspect.data(), count, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(lb + Pc.off, offs.data(), 4 * offs.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(lb + Pc.J.tcb, Pc.J.chunk_table, sizeof Pc.J.chunk_table, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(lb + Pc.J.zero0, 0, Pc.J.zero1 - Pc.J.zero0, st));
+    L.suspect = lb + Pc.suspect; L.off = (const uint32_t*)(lb + Pc.off);
+    VfyView C = V; C.M = Mc; C.rho = nullptr; C.fterm = nullptr;
+    bpv_bind_jobs(C, lb, Pc.J);
     bpv_launch_gather(V, L, C, st);
-    bpv_launch_transcript(C, st);
-    bpv_launch_scalars(C, st);
-    if ((rc = launch_msm(Dc, Mc, C.digits, C.partial, st))) return rc;
-    bpv_launch_varbase(C, st);
-    ReduceView R; R.rows = Mc; R.ntargets = 1; R.partial = C.partial; R.target_chunk_begin = (const uint16_t*)(lb + c_tcb);
-    R.enc = (uint32_t*)(lb + c_enc); R.out_off = nullptr; R.out = nullptr; R.corr = nullptr;
-    uint32_t* sums = (uint32_t*)(lb + c_sums);
-    launch_sum_ed(R, sums, st);
-    k_encode<<<dim3((Mc + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
+    if ((rc = per_job_pass(C, Dc, lb, Pc.J, st))) return rc;
     HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * M, st));
-    bpv_launch_scatter(L, R.enc, Mc, enc, M, st);
+    bpv_launch_scatter(L, (const uint32_t*)(lb + Pc.J.enc), Mc, enc, M, st);
     HIP_TRY(hipGetLastError());
     tally.jobs_again += Mc;
     *done = true;
@@ -126,49 +131,22 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
         for (uint64_t i = 0; i < n; i++) job_base[i + 1] = job_base[i] + job_counts[i];
     }
     const uint32_t M = consistency ? job_base[n] : (uint32_t)(jobs_per * n), Mw = M ? M : 1;
-    const DevLayout& D = pick_layout(S.set, Mw);
+    const DevLayout &D = pick_layout(S.set, Mw), &D1 = pick_layout(S.set, 1);
     hipStream_t st = dev().stream;
-    // workspace
-    size_t off = 0;
-    auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_jb = sz(4 * (n + 1)), o_eb = sz(4 * n),
-                 o_poff = sz(8ull * Mw), o_voff = sz(8ull * Mw), o_kind = sz(Mw), o_lgn = sz(Mw), o_bad = sz(4ull * Mw),
-                 o_pts = sz((size_t)VP_NUM * GE_W * 4 * Mw), o_scal = sz((size_t)VS_NUM * 32 * Mw),
-                 o_zero0 = off,                                                                   // ---- zero-initialised from here
-                 o_dig = sz((size_t)NBASE * DIGW * 4 * Mw), o_vs = sz((size_t)VP_NUM * 32 * Mw),
-                 o_zero1 = off,
-                 o_part = sz((size_t)(D.nchunks + VP_NUM) * GE_W * 4 * Mw), o_sums = sz((size_t)GE_W * 4 * Mw), o_enc = sz((size_t)32 * Mw), o_tcb = sz(16);
     // batch check (random linear combination, bp_verify.h RlcView): used when the batch is large enough to pay for it
     const bool batch_mode = M >= (uint32_t)env_int("ZKP_HIP_BATCH_VERIFY_MIN", (int)RLC_MIN_JOBS) && !getenv("ZKP_HIP_NO_BATCH_VERIFY");
-    const uint32_t N = VP_NUM * Mw;
-    const DevLayout& D1 = pick_layout(S.set, 1);
-    size_t o_rho = 0, o_ft = 0, o_cnt = 0, o_rz1 = 0, o_nl = 0, o_vd = 0, o_stt = 0, o_cur = 0, o_srt = 0, o_bkt = 0, o_seg = 0, o_d1 = 0, o_p1 = 0, o_s1 = 0, o_res = 0, o_tcb1 = 0;
-    if (batch_mode) {
-        o_rho = sz(32ull * Mw);
-        o_ft = sz((size_t)NBASE * 32 * Mw); o_cnt = sz((size_t)RLC_NWIN * (RLC_NBUCKET + 1) * 4); o_rz1 = off;      // [o_ft, o_rz1) zero-initialised
-        o_nl = sz((size_t)N * RLC_NIELS_W * 4); o_vd = sz((size_t)RLC_NWIN * N * 2); o_stt = sz((size_t)RLC_NWIN * (RLC_NBUCKET + 2) * 4);
-        o_cur = sz((size_t)RLC_NWIN * (RLC_NBUCKET + 1) * 4); o_srt = sz((size_t)RLC_NWIN * N * 4);
-        o_bkt = sz((size_t)RLC_NWIN * RLC_NBUCKET * GE_W * 4); o_seg = sz((size_t)RLC_NWIN * RLC_NSEG * GE_W * 4);
-        o_d1 = sz((size_t)NBASE * DIGW * 4); o_p1 = sz((size_t)D1.nchunks * GE_W * 4); o_s1 = sz((size_t)GE_W * 4); o_res = sz(64); o_tcb1 = sz(16);
-    }
-    if (off > S.cap) {
-        if (S.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(S.buf)); S.buf = nullptr; S.cap = 0; }
-        HIP_TRY(hipMalloc(&S.buf, off)); S.cap = off;
-    }
-    uint8_t* base = (uint8_t*)S.buf;
-    if (consistency) HIP_TRY(hipMemcpyAsync(base + o_jb, job_base.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));
-    const uint16_t tcb[2] = {0, (uint16_t)(D.nchunks + VP_NUM)};       // one target: the fixed chunks and the 17 proof-point products
-    HIP_TRY(hipMemcpyAsync(base + o_tcb, tcb, sizeof tcb, hipMemcpyHostToDevice, st));
-    VfyView V{};
-    V.M = M; V.in = d_proofs; V.proof_off = (uint64_t*)(base + o_poff); V.venc_off = (uint64_t*)(base + o_voff); V.kind = base + o_kind; V.lgn = base + o_lgn;
-    V.bad = (int32_t*)(base + o_bad); V.pts = (uint32_t*)(base + o_pts); V.scal = (uint32_t*)(base + o_scal); V.digits = (uint32_t*)(base + o_dig);
-    V.vscal = (uint32_t*)(base + o_vs); V.partial = (uint32_t*)(base + o_part); V.var_chunk0 = D.nchunks; V.table = dev().d_edg_table; V.wbits = dev().edg.wbits;
-    V.job_base = (const uint32_t*)(base + o_jb); V.env_bad = (int32_t*)(base + o_eb);
+    const BpvBatchPlan P = bpv_plan_batch(n, Mw, D.nchunks, batch_mode, D1.nchunks);
+    if ((rc = S.buf.reserve(P.total))) return rc;
+    uint8_t* base = S.buf.p;
+    if (consistency) HIP_TRY(hipMemcpyAsync(base + P.job_base, job_base.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(base + P.J.zero0, 0, P.J.zero1 - P.J.zero0, st));
+    HIP_TRY(hipMemcpyAsync(base + P.J.tcb, P.J.chunk_table, sizeof P.J.chunk_table, hipMemcpyHostToDevice, st));
+    VfyView V{}; V.M = M; V.in = d_proofs; V.table = dev().d_edg_table; V.wbits = dev().edg.wbits; V.job_base = (const uint32_t*)(base + P.job_base); V.env_bad = (int32_t*)(base + P.env_bad);
+    bpv_bind_jobs(V, base, P.J);
     if (scheme == ZKP_HIP_OP_RANGE) bpv_launch_parse(V, (uint32_t)n, stride, d_lens, d_mins, d_maxs, st);
     else if (scheme == ZKP_HIP_OP_THRESHOLD) bpv_launch_parse_threshold(V, (uint32_t)n, stride, d_lens, d_mins, st);
     else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_lens, st);
-    uint32_t* enc = (uint32_t*)(base + o_enc);
+    uint32_t* enc = (uint32_t*)(base + P.J.enc);
     bool accepted_as_a_batch = false, located = false;      // located: the check did not stand and localise_bp has put the suspects' encodings into enc
     std::unique_ptr<BpLocaliseTally> tally;                  // set once the batch check has not stood
     if (M) bpv_launch_decode(V, st);
@@ -184,29 +162,23 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
             const sc m = sc_from_raw256(raw);
             for (int k = 0; k < 8; k++) rho[(size_t)k * M + j] = m.v[k];
         }
-        HIP_TRY(hipMemcpyAsync(base + o_rho, rho.data(), rho.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(base + o_ft, 0, o_rz1 - o_ft, st));
-        const uint16_t tcb1[2] = {0, (uint16_t)D1.nchunks};
-        HIP_TRY(hipMemcpyAsync(base + o_tcb1, tcb1, sizeof tcb1, hipMemcpyHostToDevice, st));
-        VfyView W = V; W.rho = (const uint32_t*)(base + o_rho); W.fterm = (uint32_t*)(base + o_ft);
+        HIP_TRY(hipMemcpyAsync(base + P.rho, rho.data(), rho.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(base + P.fterm, 0, P.rzero1 - P.fterm, st));
+        VfyView W = V; W.rho = (const uint32_t*)(base + P.rho); W.fterm = (uint32_t*)(base + P.fterm);
         bpv_launch_transcript(W, st);
         bpv_launch_scalars(W, st);
-        uint32_t* dig1 = (uint32_t*)(base + o_d1); uint32_t* part1 = (uint32_t*)(base + o_p1); uint32_t* sums1 = (uint32_t*)(base + o_s1);
+        uint32_t* dig1 = (uint32_t*)(base + P.dig1); uint32_t* sums1 = (uint32_t*)(base + P.sum1);
         bpv_launch_rlc_fixed_sum(W, dig1, st);
-        if ((rc = launch_msm(D1, 1, dig1, part1, st))) return rc;
-        ReduceView R1; R1.rows = 1; R1.ntargets = 1; R1.partial = part1; R1.target_chunk_begin = (const uint16_t*)(base + o_tcb1);
-        R1.enc = nullptr; R1.out_off = nullptr; R1.out = nullptr; R1.corr = nullptr;
-        launch_sum_ed(R1, sums1, st);
-        RlcView Q{};
-        Q.N = VP_NUM * M; Q.niels = (uint32_t*)(base + o_nl); Q.dig = (int16_t*)(base + o_vd); Q.count = (uint32_t*)(base + o_cnt);
-        Q.start = (uint32_t*)(base + o_stt); Q.cursor = (uint32_t*)(base + o_cur); Q.sorted = (uint32_t*)(base + o_srt);
-        Q.bucket = (uint32_t*)(base + o_bkt); Q.seg = (uint32_t*)(base + o_seg); Q.fixed_sum = sums1; Q.result = (uint32_t*)(base + o_res);
+        if ((rc = fixed_base_sum(D1, 1, dig1, (uint32_t*)(base + P.part1), sums1, st))) return rc;
+        RlcView Q{}; Q.N = VP_NUM * M; Q.niels = (uint32_t*)(base + P.niels); Q.dig = (int16_t*)(base + P.dig); Q.count = (uint32_t*)(base + P.count);
+        Q.start = (uint32_t*)(base + P.start); Q.cursor = (uint32_t*)(base + P.cursor); Q.sorted = (uint32_t*)(base + P.sorted);
+        Q.bucket = (uint32_t*)(base + P.bucket); Q.seg = (uint32_t*)(base + P.seg); Q.fixed_sum = sums1; Q.result = (uint32_t*)(base + P.result);
         bpv_launch_rlc_points(W, Q, st);
         bpv_launch_rlc_sort(Q, st);
         bpv_launch_rlc_reduce(Q, st);
         HIP_TRY(hipGetLastError());
         uint32_t res[9] = {0};
-        HIP_TRY(hipMemcpyAsync(res, base + o_res, sizeof res, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(res, base + P.result, sizeof res, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         accepted_as_a_batch = res[8] == 1;
         if (!accepted_as_a_batch && getenv("ZKP_HIP_BP_BATCH_VERIFY_ONLY"))                           // diagnostic: the verdict of this check, no per-job pass
@@ -217,21 +189,11 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
             if ((rc = localise_bp(S, V, W, Q, (uint32_t)n, jobs_per, consistency ? job_base.data() : nullptr, enc, *tally, &located))) return rc;
             if (!located) {
                 tally->jobs_again += M;
-                HIP_TRY(hipMemsetAsync(base + o_zero0, 0, o_zero1 - o_zero0, st));                  // weighted scalars out, per-job path below
+                HIP_TRY(hipMemsetAsync(base + P.J.zero0, 0, P.J.zero1 - P.J.zero0, st));          // weighted scalars out, per-job path below
             }
         }
     }
-    if (M && !accepted_as_a_batch && !located) {
-        bpv_launch_transcript(V, st);
-        bpv_launch_scalars(V, st);
-        if ((rc = launch_msm(D, M, V.digits, V.partial, st))) return rc;
-        bpv_launch_varbase(V, st);
-        ReduceView R; R.rows = M; R.ntargets = 1; R.partial = V.partial; R.target_chunk_begin = (const uint16_t*)(base + o_tcb);
-        R.enc = enc; R.out_off = nullptr; R.out = nullptr; R.corr = nullptr;
-        uint32_t* sums = (uint32_t*)(base + o_sums);
-        launch_sum_ed(R, sums, st);
-        k_encode<<<dim3((M + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
-    }
+    if (M && !accepted_as_a_batch && !located && (rc = per_job_pass(V, D, base, P.J, st))) return rc;
     if (consistency) bpv_launch_final_ranges(V, enc, (uint32_t)n, d_ok, st);
     else bpv_launch_final(V, enc, (uint32_t)n, d_ok, jobs_per, st);
     HIP_TRY(hipGetLastError());
@@ -273,8 +235,7 @@ int verify_bp_call(int scheme, uint64_t n, const uint8_t* proofs, uint64_t strid
 
 void bpv_release_all() {
     if (!dev().vfy) return;
-    if (dev().vfy->buf) (void)hipFree(dev().vfy->buf);
-    if (dev().vfy->loc_buf) (void)hipFree(dev().vfy->loc_buf);
+    (void)hipFree(dev().vfy->buf.p); (void)hipFree(dev().vfy->loc.p);      // (a null pointer is accepted)
     free_set(dev().vfy->set);
     delete dev().vfy; dev().vfy = nullptr;
 }
