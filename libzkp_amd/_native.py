@@ -34,6 +34,9 @@ EXPORTS_BP_LOCALISE = ("zkp_hip_bp_localise_counters",)
 # symbols declared in include/libzkp_hip_composites.h (checked by tests/test_abi_composites.py)
 EXPORTS_COMPOSITES = ("zkp_hip_verify_composites", "zkp_hip_composites_counters")
 COMPOSITES_INTEGRITY_ONLY = 1     # ZKP_HIP_COMPOSITES_INTEGRITY_ONLY: digests only
+# symbols declared in include/libzkp_hip_statements.h (checked by tests/test_abi_statements.py); none of them is a zkp_hip_* name
+EXPORTS_STATEMENTS = ("zkp_stmt_verify", "zkp_stmt_verify_device", "zkp_stmt_counters")
+STMT_ACCEPTED, STMT_ENVELOPE, STMT_STATEMENT, STMT_PROOF = 0, 1, 2, 3      # ZKP_STMT_*: which step decided an envelope
 
 _lib = None
 
@@ -169,6 +172,12 @@ def lib():
             L.zkp_hip_verify_composites.restype = ctypes.c_int
             L.zkp_hip_composites_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
             L.zkp_hip_composites_counters.restype = ctypes.c_int
+        if hasattr(L, "zkp_stmt_verify"):                   # (an older build loaded through ZKP_HIP_LIB has none; api.verify_ops then raises)
+            for f in (L.zkp_stmt_verify, L.zkp_stmt_verify_device):
+                f.argtypes = [u64, vp, vp, u64, vp, vp, vp, vp]
+                f.restype = ctypes.c_int
+            L.zkp_stmt_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
+            L.zkp_stmt_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

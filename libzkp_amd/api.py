@@ -612,6 +612,74 @@ def verify_envelopes(envelopes, expect=None):
     return (ok == 1).tolist()
 
 
+def statement_ops(ops):
+    """The zkp_hip_op array and the value lists zkp_stmt_verify reads (include/libzkp_hip_statements.h) for `ops`, the tuples process_ops
+    takes plus ("equality_commitment", bytes32): (ctypes array, list of list values, set of op kinds that occur).  Only what a statement
+    consists of is filled in: a range op's value, a threshold op's values and a consistency op's data are no part of theirs."""
+    code = {"range": _native.OP_RANGE, "equality": _native.OP_EQUALITY, "equality_commitment": _native.OP_EQUALITY, "threshold": _native.OP_THRESHOLD,
+            "membership": _native.OP_MEMBERSHIP, "improvement": _native.OP_IMPROVEMENT, "consistency": _native.OP_CONSISTENCY}
+    arr = (_native.Op * max(len(ops), 1))()
+    lists = []
+    kinds = set()
+    for i, o in enumerate(ops):
+        k = o[0]
+        e = arr[i]
+        e.kind = code[k]
+        kinds.add(e.kind)
+        if k == "range":
+            e.a, e.b, e.c = (_check_u64("range op", x) for x in o[1:4])
+        elif k in ("equality", "improvement"):
+            e.a, e.b = (_check_u64(k + " op", x) for x in o[1:3])
+        elif k == "equality_commitment":
+            c = bytes(o[1])
+            if len(c) != 32:
+                raise ValueError("an expected commitment has 32 bytes")
+            e.count, e.list_off = 4, len(lists)
+            lists.extend(int.from_bytes(c[8 * j: 8 * j + 8], "little") for j in range(4))
+        elif k == "threshold":
+            e.a = _check_u64("threshold", o[2])
+        elif k == "membership":
+            e.a, e.count, e.list_off = _check_u64("membership value", o[1]), len(o[2]), len(lists)
+            lists.extend(_check_u64("set element", x) for x in o[2])
+    return arr, lists, kinds
+
+
+def verify_ops(ops, envelopes, reasons=False):
+    """The reference's verify_range / verify_equality / verify_equality_with_commitment / verify_threshold / verify_membership /
+    verify_improvement / verify_consistency for a mixed list in ONE library call (zkp_stmt_verify, include/libzkp_hip_statements.h): ops are
+    the tuples process_ops takes, envelopes[i] the proof held against ops[i]; an equality op may also be ("equality_commitment", bytes32).
+    Every statement is compared with its envelope on the GPU.  List of bools in the caller's order, or with reasons=True of (bool, why) with
+    why one of _native.STMT_ACCEPTED / _ENVELOPE / _STATEMENT / _PROOF.  Never raises on malformed envelopes (they are False)."""
+    blobs = [bytes(e) for e in envelopes]
+    n = len(blobs)
+    if len(ops) != n:
+        raise ValueError("ops, envelopes must have equal length")
+    if n == 0:
+        return []
+    arr, lists, kinds = statement_ops(ops)
+    for kind, op in ((0, _native.OP_EQUALITY), (1, _native.OP_MEMBERSHIP)):          # a Groth16 key only for the circuits whose kind occurs
+        if op in kinds:
+            _ensure_key(kind, verifier=True)
+    la = np.array(lists if lists else [0], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(b) for b in blobs), dtype=np.uint64, count=n), out=off[1:])
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    ok, why = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    _native.check(_native.lib().zkp_stmt_verify(n, ctypes.byref(arr), _P(la), len(lists), _P(blob), _P(off), _P(ok), _P(why) if reasons else None), "zkp_stmt_verify")
+    return [(bool(a == 1), int(w)) for a, w in zip(ok, why)] if reasons else (ok == 1).tolist()
+
+
+def verify_statements_counters(reset=True):
+    """What verify_ops did, summed over the shards since the last reset (zkp_stmt_counters, include/libzkp_hip_statements.h; always counted):
+    {"envelopes": envelopes seen, "refused_envelope" / "refused_statement" / "refused_proof": envelopes refused by the envelope step, the
+    statement step, their scheme's verifier, "ms": host wall time of the calls (of their slices)}.  reset=True zeroes the counters."""
+    ms, c = ctypes.c_double(), [ctypes.c_uint64() for _ in range(4)]
+    _native.check(_native.lib().zkp_stmt_counters(ctypes.byref(ms), *[ctypes.byref(x) for x in c], 1 if reset else 0), "zkp_stmt_counters")
+    return {"envelopes": int(c[0].value), "refused_envelope": int(c[1].value), "refused_statement": int(c[2].value), "refused_proof": int(c[3].value), "ms": float(ms.value)}
+
+
 def verify_equality_with_commitment_batch(proofs, commitments):
     """Batched verify_equality_with_commitment (equality_proof.rs:34-60): the envelope must carry exactly that commitment."""
     blobs = [bytes(p) for p in proofs]

@@ -139,7 +139,7 @@ inline int frame_consistency(uint64_t n, const uint64_t* data, const uint32_t* c
 }
 
 // the op's kind without the batch-wide ZKP_HIP_OP_SELF_CHECK flag: every reader of `kind` goes through this
-inline uint32_t op_kind(const zkp_hip_op& o) { return o.kind & ~ZKP_HIP_OP_SELF_CHECK; }
+ZKP_HD inline uint32_t op_kind(const zkp_hip_op& o) { return o.kind & ~ZKP_HIP_OP_SELF_CHECK; }
 inline uint64_t op_max_bytes(const zkp_hip_op& o) {
     switch (op_kind(o)) {
         case ZKP_HIP_OP_RANGE: return RANGE_PROOF_BYTES;

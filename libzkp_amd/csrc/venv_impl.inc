@@ -52,18 +52,16 @@ template <class F> int verify_scheme_passes(const SchemePass (&K)[SC_KINDS], Dev
     return 0;
 }
 
-// The call on device pointers, on the bound shard: classification, the records back, the plan, the rows, the cores, the verdicts into d_ok
-// (device, n bytes); ok_host (may be null) also receives them before the wait that ends the call.
-int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const uint8_t* d_expect, uint8_t* d_ok, uint8_t* ok_host) {
-    const auto t0 = std::chrono::steady_clock::now();
+// Everything behind the records, on the bound shard, shared by every call that classifies envelopes into VenvRecords (this file's, and
+// vst_impl.inc's against statements): the records back (`rec` receives them), the plan, the rows, the cores, then apply(V) -- the launch that
+// takes the row verdicts back to the caller's order, into d_ok (device, n bytes) -- and the wait that ends the call; ok_host (may be null)
+// receives the verdicts before it.  *passes / *live: scheme passes run / envelopes that got a row.
+template <class Apply>
+int verify_records_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const VenvRecord* d_rec, std::vector<VenvRecord>& rec, uint8_t* d_ok, uint8_t* ok_host,
+                        uint64_t* passes_out, uint64_t* live_out, Apply apply) {
     hipStream_t st = dev().stream;
     DevScope mem;
-    VenvRecord* d_rec = nullptr;
-    HIP_TRY(mem.alloc(&d_rec, sizeof(VenvRecord) * n));
-    const uint32_t lane_blocks = (uint32_t)((n + 255) / 256);
-    k_venv_classify<<<lane_blocks, 256, 0, st>>>(d_blob, d_off, d_expect, n, d_rec);
-    HIP_TRY(hipGetLastError());
-    std::vector<VenvRecord> rec(n);
+    rec.resize(n);
     HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, sizeof(VenvRecord) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<uint32_t> op_row(n);
@@ -98,12 +96,35 @@ int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_o
         const int rc = verify_scheme_passes(K, mem, &passes, [] { return 0; });
         if (rc) return rc;
     }
-    k_venv_apply<<<lane_blocks, 256, 0, st>>>(V, d_ok);
-    HIP_TRY(hipGetLastError());
+    const int arc = apply(V);
+    if (arc) return arc;
     if (ok_host) HIP_TRY(hipMemcpyAsync(ok_host, d_ok, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    *passes_out = passes; *live_out = P.live;
+    return 0;
+}
+
+// The call on device pointers, on the bound shard: classification, then verify_records_core with k_venv_apply; the verdicts into d_ok
+// (device, n bytes); ok_host (may be null) also receives them before the wait that ends the call.
+int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const uint8_t* d_expect, uint8_t* d_ok, uint8_t* ok_host) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = dev().stream;
+    DevScope mem;
+    VenvRecord* d_rec = nullptr;
+    HIP_TRY(mem.alloc(&d_rec, sizeof(VenvRecord) * n));
+    const uint32_t lane_blocks = (uint32_t)((n + 255) / 256);
+    k_venv_classify<<<lane_blocks, 256, 0, st>>>(d_blob, d_off, d_expect, n, d_rec);
+    HIP_TRY(hipGetLastError());
+    std::vector<VenvRecord> rec;
+    uint64_t passes = 0, live = 0;
+    const int rc = verify_records_core(n, d_blob, d_off, d_rec, rec, d_ok, ok_host, &passes, &live, [&](const VenvView& V) {
+        k_venv_apply<<<lane_blocks, 256, 0, st>>>(V, d_ok);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
     Device::HostCounter& C = dev().counter(ZKP_HIP_COUNTER_VERIFY_MIXED);
-    C.a += passes; C.b += P.live;
+    C.a += passes; C.b += live;
     C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }

@@ -41,6 +41,7 @@
 #include "verify_shards.h"
 #include "venv_steps.h"
 #include "composite_steps.h"
+#include "vst_steps.h"
 #include "../../include/libzkp_hip_verify.h"
 #include "../../include/libzkp_hip_bp_localise.h"
 #include "../../include/libzkp_hip_composites.h"
@@ -359,6 +360,8 @@ struct Device {
     struct BpLocaliseCounter { double ms = 0; uint64_t failed_checks = 0, segment_checks = 0, jobs_again = 0; } bp_localise;
     // zkp_hip_composites_counters (libzkp_hip_composites.h): what zkp_hip_verify_composites did on this shard (CompTally)
     struct CompositesCounter { double ms = 0; uint64_t composites = 0, malformed = 0, envelopes = 0; } composites;
+    // zkp_stmt_counters (libzkp_hip_statements.h): what zkp_stmt_verify / _device did on this shard (StmtTally)
+    struct StatementsCounter { double ms = 0; uint64_t envelopes = 0, refused_envelope = 0, refused_statement = 0, refused_proof = 0; } statements;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -1174,6 +1177,7 @@ void edg_launch_sum(const ReduceView& R, uint32_t* sums, hipStream_t st) { launc
 #include "bpv_impl.inc"
 #include "venv_impl.inc"
 #include "composite_impl.inc"
+#include "vst_impl.inc"
 
 // ================================================================================================ C ABI
 extern "C" {
@@ -1250,6 +1254,7 @@ void zkp_hip_shutdown(void) try {
         for (auto& C : d->host) C = Device::HostCounter();
         d->bp_localise = Device::BpLocaliseCounter();
         d->composites = Device::CompositesCounter();
+        d->statements = Device::StatementsCounter();
         d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;

@@ -4,6 +4,7 @@
 //! both behind a `hip` cargo feature, and route the call sites listed in INTEGRATION.md section 2 here.  Signatures,
 //! empty-vector-on-failure and `Result<_, String>` conventions are those of the CPU backends they replace.
 use super::hip_ffi as ffi;
+use super::hip_ffi_statements as ffi_statements;
 use super::hip_ffi_verify as ffi_verify;
 use super::ZkpBackend;
 use crate::utils::composition::BatchOperation;
@@ -202,14 +203,31 @@ pub fn init_all_gpus(n_gpus: u32) -> ZkpResult<()> {
 /// `self_check`: every proof is verified on the GPU against its own op before the batch is released (`ZKP_HIP_OP_SELF_CHECK`);
 /// same proof bytes, and an op whose proof is refused fails the batch as ProofGenerationFailed.
 pub fn process_batch_operations(ops: &[BatchOperation], self_check: bool) -> ZkpResult<Vec<Vec<u8>>> {
+    let (mut raw, mut lists) = raw_ops(ops);
+    let flag = if self_check { ffi::OP_SELF_CHECK } else { 0 };
+    for op in raw.iter_mut() {
+        op.kind |= flag; // a property of the whole batch: on every op or on none
+    }
+    let n = raw.len();
+    if n == 0 {
+        return Ok(vec![]);
+    }
+    if lists.is_empty() {
+        lists.push(0); // never dereferenced, keeps the pointer non-null
+    }
+    prove_raw_ops(&raw, &lists)
+}
+
+/// The ops as the C ABI takes them (`zkp_hip_op`) and the value lists they name: the one table both `zkp_hip_process_batch` and
+/// `zkp_stmt_verify` read.
+fn raw_ops(ops: &[BatchOperation]) -> (Vec<ffi::zkp_hip_op>, Vec<u64>) {
     let mut lists: Vec<u64> = Vec::new();
     let mut list = |v: &Vec<u64>| {
         let off = lists.len() as u64;
         lists.extend_from_slice(v);
         (v.len() as u32, off)
     };
-    let flag = if self_check { ffi::OP_SELF_CHECK } else { 0 };
-    let mut raw: Vec<ffi::zkp_hip_op> = ops
+    let raw: Vec<ffi::zkp_hip_op> = ops
         .iter()
         .map(|op| match op {
             BatchOperation::RangeProof { value, min, max } => ffi::zkp_hip_op { kind: ffi::OP_RANGE, count: 0, a: *value, b: *min, c: *max, list_off: 0 },
@@ -229,16 +247,11 @@ pub fn process_batch_operations(ops: &[BatchOperation], self_check: bool) -> Zkp
             }
         })
         .collect();
-    for op in raw.iter_mut() {
-        op.kind |= flag; // a property of the whole batch: on every op or on none
-    }
+    (raw, lists)
+}
+
+fn prove_raw_ops(raw: &[ffi::zkp_hip_op], lists: &[u64]) -> ZkpResult<Vec<Vec<u8>>> {
     let n = raw.len();
-    if n == 0 {
-        return Ok(vec![]);
-    }
-    if lists.is_empty() {
-        lists.push(0); // never dereferenced, keeps the pointer non-null
-    }
     let mut cap = 0u64;
     if unsafe { ffi::zkp_hip_process_batch_bytes(n as u64, raw.as_ptr(), &mut cap) } != 0 {
         return Err(ZkpError::BackendError(ffi::last_error()));
@@ -257,6 +270,35 @@ pub fn process_batch_operations(ops: &[BatchOperation], self_check: bool) -> Zkp
         return Err(to_zkp_error((st[i], format!("batch operation {} failed with status {}", i, st[i]))));
     }
     Ok((0..n).map(|i| out[off[i] as usize..off[i + 1] as usize].to_vec()).collect())
+}
+
+/// The verifier's counterpart of `process_batch_operations` (include/libzkp_hip_statements.h): `proofs[i]` is held against `ops[i]` --
+/// `verify_range(proof, min, max)`, `verify_equality(proof, val1, val2)`, `verify_threshold(proof, threshold)`, `verify_membership(proof,
+/// set)`, `verify_improvement(proof, old)`, `verify_consistency(proof)` -- for the whole mixed list in one FFI call; envelopes and statements
+/// are compared on the GPU.  A failed call (no device, a missing Groth16 key) verifies nothing: every verdict is false.
+pub fn verify_batch_operations(ops: &[BatchOperation], proofs: &[Vec<u8>]) -> Vec<bool> {
+    let n = ops.len();
+    if n == 0 || proofs.len() != n {
+        return vec![false; proofs.len()];
+    }
+    let (raw, lists) = raw_ops(ops);
+    let mut off = Vec::with_capacity(n + 1);
+    let mut blob = Vec::with_capacity(proofs.iter().map(|e| e.len()).sum::<usize>() + 1);
+    off.push(0u64);
+    for e in proofs {
+        blob.extend_from_slice(e);
+        off.push(blob.len() as u64);
+    }
+    blob.push(0); // keeps the pointer non-null for a list of empty envelopes; outside [off[0], off[n]), never read
+    let mut ok = vec![0u8; n];
+    let lp = if lists.is_empty() { std::ptr::null() } else { lists.as_ptr() };
+    let rc = unsafe {
+        ffi_statements::zkp_stmt_verify(n as u64, raw.as_ptr(), lp, lists.len() as u64, blob.as_ptr(), off.as_ptr(), ok.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if rc != 0 {
+        return vec![false; n];
+    }
+    ok.iter().map(|&v| v == 1).collect()
 }
 
 /// One FFI call for a list of envelopes of any scheme (include/libzkp_hip_verify.h): the parsing, `verify_proof_cryptographic`'s
