@@ -479,7 +479,7 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
     const size_t o_z = sz(W * K.nv), o_sd = sz((size_t)K.rx.digw * 4 * rows * nsc), o_rs = sz(W * 2), o_p1 = sz((size_t)c1->lay.nchunks * G1_JAC_W * 4 * rows),
                  o_p1c = sz((size_t)c1c->lay.nchunks * G1_JAC_W * 4 * rows), o_p2 = sz((size_t)c2->lay.nchunks * G2_JAC_W * 4 * rows),
                  o_s1 = sz((size_t)3 * G1_JAC_W * 4 * rows), o_s2 = sz((size_t)G2_JAC_W * 4 * rows), o_t1 = sz((size_t)G16_CPARTS * G1_JAC_W * 4 * rows),
-                 o_qe = sz((size_t)2 * 9 * K.m * 4 * rows);
+                 o_qe = sz((size_t)3 * 36 * K.m * rows);          // a, b, c: m nine-limb elements per row (g16_steps.h: the lane-per-proof passes)
     G16Run& RW = g16s().run[kind][lane & 1u];
     if (off > RW.cap) {
         if (RW.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(RW.buf)); RW.buf = nullptr; RW.cap = 0; }

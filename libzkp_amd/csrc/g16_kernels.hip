@@ -56,13 +56,17 @@ __global__ void __launch_bounds__(TB) k_g16_zdigits(G16View V) {
     const uint32_t row = blockIdx.x * TB + threadIdx.x;
     if (row < V.rows) step_g16_zdigits(V, blockIdx.y, row);
 }
-struct DevSync { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
-// one workgroup of m / 4 lanes = one proof; ONE polynomial's nine limb rows in LDS at a time (g16_steps.h: g16_qap_proof)
-static constexpr int QAP_TB_MAX = 256;
-__global__ void __launch_bounds__(QAP_TB_MAX) k_g16_qap(G16View V, G16Circuit C) {
-    extern __shared__ uint32_t g16_lds[];
-    G16Lds L; L.base = g16_lds; L.m = C.m;
-    g16_qap_proof(V, C, L, V.qap_evals + (size_t)blockIdx.x * 2 * 9 * C.m, blockIdx.x, threadIdx.x, blockDim.x, DevSync());
+// One pass of the QAP step, lane = proof row (g16_steps.h: g16_qap_pass_pair / g16_qap_pass_single).  blockIdx.x = group of QAP_TB rows,
+// blockIdx.y = task, blockIdx.z = polynomial: everything but the row is the same for all lanes of a workgroup, so twiddles, coset
+// factors and the CSR arrays arrive by scalar loads and the elements by one line per limb.  No LDS.  The passes of one and two stages
+// are compiled for four waves per SIMD and take 51 - 90 VGPRs; the three-stage passes (eight elements in registers) for three waves,
+// 112 - 164 VGPRs; of those the one that also scales by the coset factors spills (512 bytes of scratch per lane).
+static constexpr uint32_t QAP_TB = 256;
+template <bool DIF, int NST, int HEAD, int TAIL>
+__global__ void __launch_bounds__(QAP_TB, NST < 3 ? 4 : 3) k_g16_qap_pass(G16View V, G16Circuit C, uint32_t h, uint32_t poly0) {
+    const uint32_t row = blockIdx.x * QAP_TB + threadIdx.x;
+    if (row >= V.rows) return;
+    g16_qap_pass<DIF, NST, HEAD, TAIL>(V, C, poly0 + blockIdx.z, h, blockIdx.y, row);
 }
 __global__ void __launch_bounds__(TW) k_g16_cparts(G16View V, const uint32_t* sum_g1, uint32_t* tmp_g1) {
     ZKP_RAISE_PRIO();
@@ -163,12 +167,24 @@ template __global__ void k_g16_build_table<fq2, 40>(const uint32_t*, uint32_t, u
 // ================================================================================================ launchers
 void g16_launch_witness(const G16View& V, hipStream_t st) { k_g16_witness<<<(V.rows + TW - 1) / TW, TW, 0, st>>>(V); }
 void g16_launch_zdigits(const G16View& V, hipStream_t st) { k_g16_zdigits<<<dim3((V.rows + TB - 1) / TB, V.nv), TB, 0, st>>>(V); }
+// ZKP_HIP_G16_QAP_SHAPE = 2 | 3: the most stages a pass fuses (g16_steps.h: g16_qap_lane_schedule), read once
+static uint32_t env_qap_shape() {
+    const char* e = getenv("ZKP_HIP_G16_QAP_SHAPE");
+    return e && (e[0] == '2' || e[0] == '3') && !e[1] ? (uint32_t)(e[0] - '0') : G16_QAP_SHAPE_DEFAULT;
+}
 hipError_t g16_launch_qap(const G16View& V, const G16Circuit& C, hipStream_t st) {
-    const size_t lds = (size_t)9 * C.m * 4;             // one polynomial of nine-limb elements (18 KB at m = 512, 36 KB at m = 1024)
-    const uint32_t tb = C.m / 4;
-    if (tb < 64 || tb > (uint32_t)QAP_TB_MAX || (tb & 63u)) return hipErrorInvalidValue;      // domains of 256 .. 1024 points
-    k_g16_qap<<<V.rows, tb, lds, st>>>(V, C);
-    return hipSuccess;
+    if (C.m < 256 || C.m > 1024 || C.m != (1u << C.logm) || V.m != C.m || V.rows == 0) return hipErrorInvalidValue;      // domains of 256 .. 1024 points
+    const uint32_t ngroups = (V.rows + QAP_TB - 1) / QAP_TB;
+    static const uint32_t shape = env_qap_shape();
+    bool ok = true;
+    g16_qap_lane_schedule(C.m, C.logm, shape, [&](bool dif, int nst, int head, int tail, uint32_t h, uint32_t ntasks, uint32_t npoly, uint32_t poly0) {
+        const dim3 grid(ngroups, ntasks, npoly);
+#define QAP_PASS(D, N, H, T) if (dif == D && nst == N && head == H && tail == T) { k_g16_qap_pass<D, N, H, T><<<grid, QAP_TB, 0, st>>>(V, C, h, poly0); return; }
+        G16_QAP_LANE_VARIANTS(QAP_PASS)
+#undef QAP_PASS
+        ok = false;                                        // a pass the schedule names and no kernel implements
+    });
+    return ok ? hipSuccess : hipErrorInvalidValue;
 }
 void g16_launch_cparts(const G16View& V, const uint32_t* sum_g1, uint32_t* tmp_g1, hipStream_t st) {
     k_g16_cparts<<<dim3((V.rows + TW - 1) / TW, G16_CPARTS), TW, 0, st>>>(V, sum_g1, tmp_g1);

@@ -3,9 +3,9 @@
 // Groth16::<Bn254>::prove does at snark.rs:364,442 (ark-groth16 create_proof_with_reduction + LibsnarkReduction
 // witness map; restated in oracle/py/groth16.py and SURVEY.md appendix A.4).
 //
-// MI355X-first structure: one lane = one proof for witness generation and final assembly; one workgroup = one proof
-// for the QAP division (all seven size-m NTTs of a proof stay in LDS); every MSM is a fixed-base, lane = proof,
-// LDS-streamed-window kernel over the proving key's points (same kernel template as the Bulletproofs path).
+// MI355X-first structure: one lane = one proof for witness generation, the QAP division (the seven size-m NTTs of a proof,
+// pass by pass over a [poly][element][limb][rows] buffer; g16_qap_proof below is the host reference of the same arithmetic)
+// and final assembly; every MSM is a fixed-base, lane = proof kernel over the proving key's window tables.
 #pragma once
 #include "bn254_g.h"
 #include "bn254_fr9.h"
@@ -107,7 +107,7 @@ struct G16View {
     uint32_t* z;                              // [nv][8][rows] full assignment (instance block first), Montgomery Fr
     uint32_t* sdig;                           // [nscalars][rx.digw][rows] packed digits: z_k (nv), h_i (m-1), r, s, -rs, one
     uint32_t* rs;                             // [2][8][rows] raw canonical r, s (for the variable-base part of C)
-    uint32_t* qap_evals;                      // [rows][2][9][m] the QAP step's coset evaluations of a and b while c is transformed
+    uint32_t* qap_evals;                      // [3][m][9][rows] the QAP step's polynomials a, b, c, nine-limb elements, transformed in place
     // output
     uint8_t* out; uint64_t stride;            // envelope per row
 };
@@ -212,6 +212,8 @@ ZKP_HD inline uint32_t g16_bitrev(uint32_t x, uint32_t bits) {
 }
 
 // The QAP witness map of ONE proof (LibsnarkReduction::witness_map_from_matrices), `nthreads` lanes cooperating, `sync` the workgroup barrier.
+// Since the lane-per-proof passes further down replaced the kernel that ran it, this is the HOST REFERENCE of the step: tests/emul
+// compiles it, and the passes are checked against it word for word.  What follows describes it as the kernel it was.
 //
 // Round 4: ONE polynomial in LDS at a time, every pass of a transform does TWO butterfly stages, m / 4 lanes per proof.
 // Rounds 1-3 kept a, b and c in LDS together (54 / 108 KB: two / one workgroup per CU) and ran one radix-2 stage per barrier on 512 lanes
@@ -340,6 +342,191 @@ ZKP_HD inline void g16_qap_proof(const G16View& V, const G16Circuit& C, const G1
     g16_pointwise(C, L, scratch, scratch + (size_t)9 * C.m, tid, nthreads); sync();          // (a*b - c) / Z(g w^j)
     g16_transform_dif(C, L, C.tw_inv, tid, nthreads, sync);                                  // coset iFFT, bit-reversed out
     g16_store_h_bitrev(V, C, L, row, tid, nthreads);                                         // /m, g^-i, digits
+}
+
+// ---- The same witness map with ONE LANE PER PROOF ROW (k_g16_qap_pass): the shape of the MSM kernels.  A lane handles one task of one
+// pass -- the four elements of a fused stage pair, or the two of a single stage -- for its row; every index of the task (butterfly
+// position, twiddle, CSR row, bit-reversed position) is the same for all lanes, so the tables come in by scalar loads, and every data
+// access is a line of one limb of one element across consecutive rows.  No LDS, no barrier, no swizzle: the three polynomials live in
+// V.qap_evals, [3 polys][m elements][9 limbs][rows] words, and every pass transforms them in place (the tasks of a pass touch disjoint
+// elements).  The arithmetic is g16_stage_pair's / g16_stage_single's: the same butterflies in the same order on the same element
+// indices with the same twiddles, and the passes follow g16_qap_proof's sequence, so every value is the value that function holds.
+// A pass fuses two stages, or three (g16_qap_pass_triple); g16_qap_lane_schedule lists the passes of either shape.  No pass only copies
+// or only scales:
+//   HEAD_ROWS  the first decimation-in-frequency pass of a, b, c computes its inputs from z (g16_qap_load's row products);
+//   TAIL_COSET the last one multiplies by coset[bitrev(p)] (g16_scale_bitrev);
+//   HEAD_QUOT  the first pass of the final transform forms (a b - c) zinv from the three buffers (g16_pointwise), writing into c's;
+//   TAIL_H     its last pass multiplies by coset_inv[i] and writes the digits of h_i (g16_store_h_bitrev).
+enum { G16_HEAD_BUF = 0, G16_HEAD_ROWS = 1, G16_HEAD_QUOT = 2 };
+enum { G16_TAIL_BUF = 0, G16_TAIL_COSET = 1, G16_TAIL_H = 2 };
+// element e of polynomial `poly`: nine limb lines of `rows` words.  The element's address is the same for all lanes; a lane adds the
+// 32-bit byte offset of (limb, row) inside the element (9 rows words < 2^30), the same nine offsets for every element it touches: the
+// scalar-base + lane-offset form of a global access, and nine address registers for a whole pass.
+ZKP_HD inline uint32_t* g16_qe_elem(const G16View& V, uint32_t poly, uint32_t e) { return V.qap_evals + ((size_t)poly * V.m + e) * 9 * V.rows; }
+ZKP_HD inline fr9 ld_fr9_col(const uint32_t* q, uint32_t rows, uint32_t row) {
+    fr9 r;
+    ZKP_UNROLL for (uint32_t k = 0; k < 9; k++) r.v[k] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(q) + (k * rows + row) * 4u);
+    return r;
+}
+ZKP_HD inline void st_fr9_col(uint32_t* q, uint32_t rows, uint32_t row, const fr9& a) {
+    ZKP_UNROLL for (uint32_t k = 0; k < 9; k++) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(q) + (k * rows + row) * 4u) = a.v[k];
+}
+// element e of polynomial `poly` as the pass takes it in
+template <int HEAD>
+ZKP_HD inline fr9 g16_lane_head(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t e, uint32_t row) {
+    if (HEAD == G16_HEAD_ROWS) {
+        const uint32_t nc = C.n_rows;
+        const uint32_t *ptr = poly == 0 ? C.a_ptr : poly == 1 ? C.b_ptr : C.c_ptr, *col = poly == 0 ? C.a_col : poly == 1 ? C.b_col : C.c_col,
+                       *coef = poly == 0 ? C.a_coef : poly == 1 ? C.b_coef : C.c_coef;
+        fr a = fp_zero<FrParams>();
+        if (e < nc) a = g16_row_dot_fast(ptr, col, coef, e, V.z, row, V.rows);
+        else if (poly == 0 && e < nc + V.n_inst) a = ld_fr(V.z, e - nc, row, V.rows);
+        return fr9_from_fr(a);
+    }
+    if (HEAD == G16_HEAD_QUOT) {
+        const fr9 a = ld_fr9_col(g16_qe_elem(V, 0, e), V.rows, row), b = ld_fr9_col(g16_qe_elem(V, 1, e), V.rows, row);
+        return fr9_mul(fr9_sub_k<32>(fr9_mul(a, b), ld_fr9_col(g16_qe_elem(V, 2, e), V.rows, row)), ld_fr9_c(C.zinv, 0));
+    }
+    return ld_fr9_col(g16_qe_elem(V, poly, e), V.rows, row);
+}
+// what the pass leaves of the element at position p: the element, or its product with the table entry of p's coefficient index (the
+// factor).  A pass forms all its results before its first store, so that the factors, like the twiddles, come in by scalar loads.
+template <int TAIL>
+ZKP_HD inline fr9 g16_lane_tail_factor(const G16Circuit& C, uint32_t p) {
+    if (TAIL == G16_TAIL_BUF) return fr9{};
+    return ld_fr9_c(TAIL == G16_TAIL_COSET ? C.coset : C.coset_inv, g16_bitrev(p, C.logm));
+}
+template <int TAIL>
+ZKP_HD inline fr9 g16_lane_tail_value(const fr9& x, const fr9& f) { return TAIL == G16_TAIL_BUF ? x : fr9_mul(x, f); }
+template <int TAIL>
+ZKP_HD inline void g16_lane_tail_store(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t p, const fr9& y, uint32_t row) {
+    if (TAIL == G16_TAIL_H) {
+        const uint32_t i = g16_bitrev(p, C.logm);             // coefficient index of the element at position p
+        if (i + 1 < C.m) st_fr_digits(V.sdig, g16_sc_h(V) + i, row, V.rows, fr9_to_fr<FrParams>(y), V.rx);
+        return;
+    }
+    st_fr9_col(g16_qe_elem(V, poly, p), V.rows, row, y);
+}
+// task q < m / 4 of a fused pass over the stages with half-lengths (2h, h) / (h, 2h): g16_stage_pair for one row.  Everything is
+// loaded, and every result formed, before the first store, so that the table reads stay scalar loads.
+template <bool DIF, int HEAD, int TAIL>
+ZKP_HD inline void g16_qap_pass_pair(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t h, uint32_t q, uint32_t row) {
+    const uint32_t* tw = DIF ? C.tw_inv : C.tw;
+    const uint32_t s1 = C.m / (2 * h), s2 = C.m / (4 * h);
+    const uint32_t grp = q / h, j = q % h, e0 = grp * 4 * h + j;
+    const fr9 wh = ld_fr9_c(tw, j * s1), wa = ld_fr9_c(tw, j * s2), wb = ld_fr9_c(tw, (j + h) * s2);
+    const fr9 f0 = g16_lane_tail_factor<TAIL>(C, e0), f1 = g16_lane_tail_factor<TAIL>(C, e0 + h), f2 = g16_lane_tail_factor<TAIL>(C, e0 + 2 * h),
+              f3 = g16_lane_tail_factor<TAIL>(C, e0 + 3 * h);
+    fr9 x0 = g16_lane_head<HEAD>(V, C, poly, e0, row), x1 = g16_lane_head<HEAD>(V, C, poly, e0 + h, row), x2 = g16_lane_head<HEAD>(V, C, poly, e0 + 2 * h, row),
+        x3 = g16_lane_head<HEAD>(V, C, poly, e0 + 3 * h, row);
+    if (DIF) { g16_bf_dif(x0, x2, wa); g16_bf_dif(x1, x3, wb); g16_bf_dif(x0, x1, wh); g16_bf_dif(x2, x3, wh); }
+    else { g16_bf_dit(x0, x1, wh); g16_bf_dit(x2, x3, wh); g16_bf_dit(x0, x2, wa); g16_bf_dit(x1, x3, wb); }
+    x0 = g16_lane_tail_value<TAIL>(x0, f0); x1 = g16_lane_tail_value<TAIL>(x1, f1); x2 = g16_lane_tail_value<TAIL>(x2, f2); x3 = g16_lane_tail_value<TAIL>(x3, f3);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0, x0, row); g16_lane_tail_store<TAIL>(V, C, poly, e0 + h, x1, row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 2 * h, x2, row); g16_lane_tail_store<TAIL>(V, C, poly, e0 + 3 * h, x3, row);
+}
+// task k < m / 2 of a stage on its own (the odd stage of m = 512: the first of a decimation-in-frequency transform, the last of a
+// decimation-in-time one): g16_stage_single for one row
+template <bool DIF, int HEAD>
+ZKP_HD inline void g16_qap_pass_single(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t half, uint32_t k, uint32_t row) {
+    const uint32_t len = 2 * half, tstride = C.m / len;
+    const uint32_t grp = k / half, j = k % half, i0 = grp * len + j, i1 = i0 + half;
+    const fr9 w = ld_fr9_c(DIF ? C.tw_inv : C.tw, j * tstride);
+    fr9 u = g16_lane_head<HEAD>(V, C, poly, i0, row), v = g16_lane_head<HEAD>(V, C, poly, i1, row);
+    if (DIF) g16_bf_dif(u, v, w); else g16_bf_dit(u, v, w);
+    g16_lane_tail_store<G16_TAIL_BUF>(V, C, poly, i0, u, row); g16_lane_tail_store<G16_TAIL_BUF>(V, C, poly, i1, v, row);
+}
+// task q < m / 8 of a fused pass over three stages, half-lengths (4h, 2h, h) / (h, 2h, 4h): eight elements e0 + c h.  Stage by stage the
+// butterflies, element indices and twiddles are those of g16_stage_single / g16_stage_pair run over the same half-lengths (half-length 4h:
+// elements c and c + 4 with tw[(j + c h) m / 8h]; 2h: g16_stage_pair's wa, wb in either half of the eight; h: its wh), so every value is the
+// one the two-stage passes hold: which stages share a pass changes where an element waits between them and nothing else.
+template <bool DIF, int HEAD, int TAIL>
+ZKP_HD inline void g16_qap_pass_triple(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t h, uint32_t q, uint32_t row) {
+    const uint32_t* tw = DIF ? C.tw_inv : C.tw;
+    const uint32_t s1 = C.m / (2 * h), s2 = C.m / (4 * h), s4 = C.m / (8 * h);
+    const uint32_t grp = q / h, j = q % h, e0 = grp * 8 * h + j;
+    fr9 x[8];
+    x[0] = g16_lane_head<HEAD>(V, C, poly, e0, row); x[1] = g16_lane_head<HEAD>(V, C, poly, e0 + h, row);
+    x[2] = g16_lane_head<HEAD>(V, C, poly, e0 + 2 * h, row); x[3] = g16_lane_head<HEAD>(V, C, poly, e0 + 3 * h, row);
+    x[4] = g16_lane_head<HEAD>(V, C, poly, e0 + 4 * h, row); x[5] = g16_lane_head<HEAD>(V, C, poly, e0 + 5 * h, row);
+    x[6] = g16_lane_head<HEAD>(V, C, poly, e0 + 6 * h, row); x[7] = g16_lane_head<HEAD>(V, C, poly, e0 + 7 * h, row);
+    if (DIF) {
+        ZKP_UNROLL for (uint32_t c = 0; c < 4; c++) g16_bf_dif(x[c], x[c + 4], ld_fr9_c(tw, (j + c * h) * s4));
+        const fr9 wa = ld_fr9_c(tw, j * s2), wb = ld_fr9_c(tw, (j + h) * s2);
+        ZKP_UNROLL for (uint32_t c = 0; c < 8; c += 4) { g16_bf_dif(x[c], x[c + 2], wa); g16_bf_dif(x[c + 1], x[c + 3], wb); }
+        const fr9 wh = ld_fr9_c(tw, j * s1);
+        ZKP_UNROLL for (uint32_t c = 0; c < 8; c += 2) g16_bf_dif(x[c], x[c + 1], wh);
+    } else {
+        const fr9 wh = ld_fr9_c(tw, j * s1);
+        ZKP_UNROLL for (uint32_t c = 0; c < 8; c += 2) g16_bf_dit(x[c], x[c + 1], wh);
+        const fr9 wa = ld_fr9_c(tw, j * s2), wb = ld_fr9_c(tw, (j + h) * s2);
+        ZKP_UNROLL for (uint32_t c = 0; c < 8; c += 4) { g16_bf_dit(x[c], x[c + 2], wa); g16_bf_dit(x[c + 1], x[c + 3], wb); }
+        ZKP_UNROLL for (uint32_t c = 0; c < 4; c++) g16_bf_dit(x[c], x[c + 4], ld_fr9_c(tw, (j + c * h) * s4));
+    }
+    // eight results: each is formed and stored in turn (formed side by side they spill), so the factors of the later ones are read after
+    // a store and come in by lane loads of one address instead of scalar loads
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 0 * h, g16_lane_tail_value<TAIL>(x[0], g16_lane_tail_factor<TAIL>(C, e0 + 0 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 1 * h, g16_lane_tail_value<TAIL>(x[1], g16_lane_tail_factor<TAIL>(C, e0 + 1 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 2 * h, g16_lane_tail_value<TAIL>(x[2], g16_lane_tail_factor<TAIL>(C, e0 + 2 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 3 * h, g16_lane_tail_value<TAIL>(x[3], g16_lane_tail_factor<TAIL>(C, e0 + 3 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 4 * h, g16_lane_tail_value<TAIL>(x[4], g16_lane_tail_factor<TAIL>(C, e0 + 4 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 5 * h, g16_lane_tail_value<TAIL>(x[5], g16_lane_tail_factor<TAIL>(C, e0 + 5 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 6 * h, g16_lane_tail_value<TAIL>(x[6], g16_lane_tail_factor<TAIL>(C, e0 + 6 * h)), row);
+    g16_lane_tail_store<TAIL>(V, C, poly, e0 + 7 * h, g16_lane_tail_value<TAIL>(x[7], g16_lane_tail_factor<TAIL>(C, e0 + 7 * h)), row);
+}
+// one task of a pass over NST stages (1: h is the stage's half-length; 2, 3: the smallest of the pass's half-lengths)
+template <bool DIF, int NST, int HEAD, int TAIL>
+ZKP_HD inline void g16_qap_pass(const G16View& V, const G16Circuit& C, uint32_t poly, uint32_t h, uint32_t q, uint32_t row) {
+    static_assert(NST >= 1 && NST <= 3 && (NST > 1 || TAIL == G16_TAIL_BUF), "passes of one, two or three stages; a stage on its own has no tail");
+    if constexpr (NST == 1) g16_qap_pass_single<DIF, HEAD>(V, C, poly, h, q, row);
+    else if constexpr (NST == 2) g16_qap_pass_pair<DIF, HEAD, TAIL>(V, C, poly, h, q, row);
+    else g16_qap_pass_triple<DIF, HEAD, TAIL>(V, C, poly, h, q, row);
+}
+// The passes of the whole step in launch order, for the kernel launcher and the host emulation alike.  `shape` = the most stages a pass
+// fuses: 2 -- [1 +] 2 + 2 + ... (the odd stage first in frequency order) -- or 3 -- 3 + 3 + 3 at m = 512, 3 + 3 + 2 + 2 at m = 1024, the
+// two-stage passes at the short half-lengths.  `run(dif, nst, head, tail, h, ntasks, npoly, poly0)` is called once per launch; the launch
+// covers tasks 0 .. ntasks - 1 of polynomials poly0 .. poly0 + npoly - 1: a, b and c share one wherever their transforms are at the same
+// stage.  Shape 2: fifteen launches for either circuit; shape 3: nine (m = 512) and twelve (m = 1024).
+constexpr uint32_t G16_QAP_SHAPE_DEFAULT = 2;
+inline uint32_t g16_qap_lane_stage_counts(uint32_t logm, uint32_t shape, uint32_t cnt[32]) {
+    uint32_t n = 0;
+    if (shape == 3) {
+        const uint32_t pairs = logm % 3 == 1 ? 2u : logm % 3 == 2 ? 1u : 0u;
+        for (uint32_t i = 0; i < (logm - 2 * pairs) / 3; i++) cnt[n++] = 3;
+        for (uint32_t i = 0; i < pairs; i++) cnt[n++] = 2;
+    } else {
+        if (logm & 1u) cnt[n++] = 1;
+        for (uint32_t i = 0; i < logm / 2; i++) cnt[n++] = 2;
+    }
+    return n;
+}
+template <class Run>
+inline void g16_qap_lane_schedule(uint32_t m, uint32_t logm, uint32_t shape, Run run) {
+    uint32_t cnt[32]; const uint32_t n = g16_qap_lane_stage_counts(logm, shape, cnt);      // n >= 2 for logm >= 4
+    for (int fin = 0; fin < 2; fin++) {
+        const uint32_t npoly = fin ? 1u : 3u, poly0 = fin ? 2u : 0u;
+        const int head = fin ? G16_HEAD_QUOT : G16_HEAD_ROWS, tail = fin ? G16_TAIL_H : G16_TAIL_COSET;
+        uint32_t half = m / 2;                                                        // decimation in frequency: half-lengths m / 2 ... 1
+        for (uint32_t i = 0; i < n; half >>= cnt[i], i++)
+            run(true, (int)cnt[i], i == 0 ? head : G16_HEAD_BUF, i + 1 == n ? tail : G16_TAIL_BUF, half >> (cnt[i] - 1), m >> cnt[i], npoly, poly0);
+        if (fin) break;
+        uint32_t h = 1;                                                               // decimation in time: half-lengths 1 ... m / 2
+        for (uint32_t i = n; i-- > 0; h <<= cnt[i]) run(false, (int)cnt[i], G16_HEAD_BUF, G16_TAIL_BUF, h, m >> cnt[i], npoly, poly0);
+    }
+}
+// the combinations of (decimation in frequency, stages, head, tail) the two shapes use: one kernel each
+#define G16_QAP_LANE_VARIANTS(X) \
+    X(true, 1, G16_HEAD_ROWS, G16_TAIL_BUF) X(true, 1, G16_HEAD_QUOT, G16_TAIL_BUF) X(false, 1, G16_HEAD_BUF, G16_TAIL_BUF) \
+    X(true, 2, G16_HEAD_ROWS, G16_TAIL_BUF) X(true, 2, G16_HEAD_QUOT, G16_TAIL_BUF) X(true, 2, G16_HEAD_BUF, G16_TAIL_BUF) \
+    X(true, 2, G16_HEAD_BUF, G16_TAIL_COSET) X(true, 2, G16_HEAD_BUF, G16_TAIL_H) X(false, 2, G16_HEAD_BUF, G16_TAIL_BUF) \
+    X(true, 3, G16_HEAD_ROWS, G16_TAIL_BUF) X(true, 3, G16_HEAD_QUOT, G16_TAIL_BUF) X(true, 3, G16_HEAD_BUF, G16_TAIL_BUF) \
+    X(true, 3, G16_HEAD_BUF, G16_TAIL_COSET) X(true, 3, G16_HEAD_BUF, G16_TAIL_H) X(false, 3, G16_HEAD_BUF, G16_TAIL_BUF)
+// one task by its run-time description (the host form; false: a pass that has no step function)
+inline bool g16_qap_lane_task(const G16View& V, const G16Circuit& C, bool dif, int nst, int head, int tail, uint32_t h, uint32_t poly, uint32_t q, uint32_t row) {
+#define G16_QAP_LANE_HOST(D, N, H, T) if (dif == D && nst == N && head == H && tail == T) { g16_qap_pass<D, N, H, T>(V, C, poly, h, q, row); return true; }
+    G16_QAP_LANE_VARIANTS(G16_QAP_LANE_HOST)
+#undef G16_QAP_LANE_HOST
+    return false;
 }
 
 // ---- final assembly.  thread = proof.  sums: [4 targets][words][rows] Jacobian sums A (G1), B1 (G1), Cp (G1), B2 (G2)

@@ -34,8 +34,8 @@ def main():
     for r, n in zip(rows, names):
         lines.append("| %s | `%s` | %s | %s | %s | %s | %s | %s | %s |" % (r["unit"], n, r.get("VGPRs"), r.get("AGPRs"), r.get("TotalSGPRs"), r.get("VGPRs Spill"),
                                                                        r.get("ScratchSize"), r.get("LDS Size"), r.get("Occupancy")))
-    lines += ["", "Dynamic LDS is not in these figures: k_fq2vm 41-159 KB per chain and k_g16_qap 18 / 36 KB (launch-time), which is what limits those "
-              "kernels to one workgroup per CU.  k_msm_gather<G1Msm / G2Msm> (the Groth16 MSMs) use no LDS."]
+    lines += ["", "Dynamic LDS is not in these figures: k_fq2vm 41-159 KB per chain (launch-time), which is what limits that "
+              "kernel to one workgroup per CU.  k_msm_gather<G1Msm / G2Msm> (the Groth16 MSMs) and k_g16_qap_pass (the QAP step) use no LDS."]
     open(out, "w").write("\n".join(lines) + "\n")
 
 
