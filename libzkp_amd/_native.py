@@ -37,6 +37,9 @@ COMPOSITES_INTEGRITY_ONLY = 1     # ZKP_HIP_COMPOSITES_INTEGRITY_ONLY: digests o
 # symbols declared in include/libzkp_hip_statements.h (checked by tests/test_abi_statements.py); none of them is a zkp_hip_* name
 EXPORTS_STATEMENTS = ("zkp_stmt_verify", "zkp_stmt_verify_device", "zkp_stmt_counters")
 STMT_ACCEPTED, STMT_ENVELOPE, STMT_STATEMENT, STMT_PROOF = 0, 1, 2, 3      # ZKP_STMT_*: which step decided an envelope
+# symbols declared in include/libzkp_hip_seal.h (checked by tests/test_abi_seal.py); none of them is a zkp_* name
+EXPORTS_SEAL = ("libzkp_seal_composites", "libzkp_seal_batch", "libzkp_seal_counters")
+SEAL_FAILED_OP, SEAL_SEALED, SEAL_REFUSED, SEAL_UNREADABLE = 0, 1, 2, 3      # LIBZKP_SEAL_*: the status of a container
 
 _lib = None
 
@@ -178,6 +181,13 @@ def lib():
                 f.restype = ctypes.c_int
             L.zkp_stmt_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
             L.zkp_stmt_counters.restype = ctypes.c_int
+        if hasattr(L, "libzkp_seal_composites"):            # (an older build loaded through ZKP_HIP_LIB has none; composite.create_composite_proofs then raises)
+            L.libzkp_seal_composites.argtypes = [u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp]
+            L.libzkp_seal_composites.restype = ctypes.c_int
+            L.libzkp_seal_batch.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp, vp]
+            L.libzkp_seal_batch.restype = ctypes.c_int
+            L.libzkp_seal_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
+            L.libzkp_seal_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

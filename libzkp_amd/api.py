@@ -908,6 +908,24 @@ def process_ops(ops, seeds=None, self_check=False):
     n = len(ops)
     if n == 0:
         return []
+    arr, la, cap, sp = _marshal_ops(ops, seeds, self_check)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    st = np.zeros(n, dtype=np.int32)
+    rc = _native.lib().zkp_hip_process_batch(n, ctypes.byref(arr), _P(la), sp, _P(out), cap, _P(off), _P(st))
+    if rc < 0:
+        raise ZkpBackendError("Backend error: %s" % _native.last_error())
+    if rc != 0:
+        i = int(np.nonzero(st)[0][0])
+        raise ZkpBackendError("Proof generation failed: operation %d (%s) failed with status %d" % (i, ops[i][0], int(st[i])))
+    raw = out.tobytes()
+    return [raw[int(off[i]): int(off[i + 1])] for i in range(n)]
+
+
+def _marshal_ops(ops, seeds, self_check):
+    """The op tuples of batch_add_* as the C ABI takes them: (zkp_hip_op array, value lists, an upper bound of the proofs' bytes, seeds
+    pointer or None).  Loads the Groth16 keys the ops need."""
+    n = len(ops)
     seeds = None if seeds is None else bytes(seeds)
     if seeds is not None and len(seeds) != 32 * n:
         raise ValueError("seeds must hold 32 bytes per op")
@@ -936,18 +954,66 @@ def process_ops(ops, seeds=None, self_check=False):
             e.count, e.list_off = len(o[1]), len(lists); lists.extend(o[1])
             cap += 10 + 4 + 32 * len(o[1]) + (4 + 672 + 32) * max(len(o[1]) - 1, 0) + 32
     la = np.array(lists if lists else [0], dtype=np.uint64)
-    out = np.zeros(max(cap, 1), dtype=np.uint8)
-    off = np.zeros(n + 1, dtype=np.uint64)
-    st = np.zeros(n, dtype=np.int32)
-    sp = None if seeds is None else ctypes.c_char_p(seeds)
-    rc = _native.lib().zkp_hip_process_batch(n, ctypes.byref(arr), _P(la), sp, _P(out), cap, _P(off), _P(st))
+    return arr, la, cap, None if seeds is None else ctypes.c_char_p(seeds)
+
+
+def process_ops_sealed(ops, counts, metadata=None, seeds=None, self_check=False):
+    """process_ops followed by create_composite_proof / create_proof_with_metadata per group of ops, without the proofs leaving the GPU in
+    between: the batch is staged and proved, libzkp_seal_batch (include/libzkp_hip_seal.h) frames and hashes container i from the proofs
+    of the next counts[i] consecutive ops where they lie in HBM (a batch staged on several shards is fetched once first), and the batch
+    is freed.  metadata: None, or one dict (str -> bytes) per container, written in dict order.  Returns the containers as a list of
+    bytes, the same bytes the host functions give for process_ops' proofs under the same seeds."""
+    from . import composite
+    n, m = len(ops), len(counts)
+    if sum(int(c) for c in counts) != n or any(int(c) < 0 for c in counts):
+        raise ValueError("counts must be non-negative and sum to the number of ops")
+    if metadata is not None and len(metadata) != m:
+        raise ValueError("metadata must hold one dict per container")
+    if m == 0:
+        return []
+    for i, c in enumerate(counts):
+        if int(c) == 0:
+            raise ValueError("proof list cannot be empty")            # create_composite_proof's error, before anything is proved
+    L = _native.lib()
+    if not hasattr(L, "libzkp_seal_batch"):
+        raise _native.NativeError("this build of libzkp_hip.so has no libzkp_seal_batch")
+    arr, la, cap, sp = _marshal_ops(ops, seeds, self_check)
+    first = composite.seal_offsets([int(c) for c in counts])
+    meta_blob = meta_off = None
+    if metadata is not None:
+        wires = [composite._metadata_wire(md) for md in metadata]
+        meta_blob, meta_off = np.frombuffer(b"".join(wires) or b"\0", dtype=np.uint8), composite.seal_offsets([len(w) for w in wires])
+    total_cap = cap + 4 * n + 44 * m + (int(meta_off[-1]) if meta_off is not None else 0)          # an upper bound: every container sealed
+    out, out_off, status = np.empty(max(total_cap, 1), dtype=np.uint8), np.zeros(m + 1, dtype=np.uint64), np.zeros(m, dtype=np.uint8)
+    ptr = lambda a: None if a is None else _P(a)  # noqa: E731
+    batch = ctypes.c_void_p()
+    rc = L.zkp_hip_batch_stage(n, ctypes.byref(arr), _P(la), sp, ctypes.byref(batch))
     if rc < 0:
         raise ZkpBackendError("Backend error: %s" % _native.last_error())
-    if rc != 0:
-        i = int(np.nonzero(st)[0][0])
-        raise ZkpBackendError("Proof generation failed: operation %d (%s) failed with status %d" % (i, ops[i][0], int(st[i])))
-    raw = out.tobytes()
-    return [raw[int(off[i]): int(off[i + 1])] for i in range(n)]
+    try:
+        rc = L.zkp_hip_batch_prove_async(batch)
+        if rc == 0:
+            rc = L.libzkp_seal_batch(batch, m, _P(first), ptr(meta_blob), ptr(meta_off), _P(out), total_cap, _P(out_off), _P(status))
+        if rc < 0:
+            raise ZkpBackendError("Backend error: %s" % _native.last_error())
+    finally:
+        L.zkp_hip_batch_free(batch)
+    for i in np.flatnonzero(status != _native.SEAL_SEALED):
+        i = int(i)
+        if status[i] == _native.SEAL_FAILED_OP:
+            raise ZkpBackendError("Proof generation failed: an operation of container %d (ops %d .. %d) failed" % (i, int(first[i]), int(first[i + 1]) - 1))
+        raise ValueError("composite proof %d would not be read back: %s" % (i, composite._unreadable_reason(range(int(counts[i])), metadata[i] if metadata is not None else {})))
+    raw = out[:int(out_off[-1])].tobytes()
+    return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(m)]
+
+
+def seal_counters(reset=True):
+    """What create_composite_proofs and process_ops_sealed did, summed over the shards since the last reset (libzkp_seal_counters,
+    include/libzkp_hip_seal.h; always counted): {"containers": containers seen, "sealed": containers written, "envelopes": their inner
+    proofs, "bytes": their bytes, "ms": host wall time of the device half of the calls}.  reset=True zeroes the counters."""
+    ms, a, b, c, d = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().libzkp_seal_counters(ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d), 1 if reset else 0), "libzkp_seal_counters")
+    return {"containers": int(a.value), "sealed": int(b.value), "envelopes": int(c.value), "bytes": int(d.value), "ms": float(ms.value)}
 
 
 KINDS = ("range", "threshold", "consistency", "equality", "membership", "improvement")

@@ -127,6 +127,82 @@ def create_proof_with_metadata(proof_data, metadata):
     return _serialize_composite([proof], {str(k): bytes(v) for k, v in metadata.items()})
 
 
+def _metadata_wire(metadata):
+    """a metadata dict (str -> bytes) in wire form, in dict order: (u32 key_len | key | u32 value_len | value)*"""
+    out = b""
+    for k, v in metadata.items():
+        kb, v = str(k).encode("utf-8"), bytes(v)
+        out += len(kb).to_bytes(4, "little") + kb + len(v).to_bytes(4, "little") + v
+    return out
+
+
+def _unreadable_reason(proofs, metadata):
+    """why the library does not seal what the reference would write: CompositeProof::from_bytes would refuse to read it back"""
+    if len(proofs) > 1000 or len(metadata) > 1000:
+        return "composite proof has too many items: proofs=%d, metadata=%d" % (len(proofs), len(metadata))
+    for k, v in metadata.items():
+        if len(str(k).encode("utf-8")) > 1024:
+            return "metadata key too large: key_len=%d" % len(str(k).encode("utf-8"))
+        if len(bytes(v)) > 65536:
+            return "metadata value too large: value_len=%d" % len(bytes(v))
+    return "composite proof too large: max %d bytes" % MAX_COMPOSITE_PROOF_BYTES
+
+
+def seal_offsets(lengths):
+    """n lengths -> the n + 1 offsets of a packed list (uint64)"""
+    import numpy as np
+    off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    if len(lengths):
+        np.cumsum(np.fromiter(lengths, dtype=np.uint64, count=len(lengths)), out=off[1:])
+    return off
+
+
+def create_composite_proofs(proof_lists, metadata=None, errors="raise"):
+    """create_composite_proof / create_proof_with_metadata for a list of containers in ONE library call (libzkp_seal_composites,
+    include/libzkp_hip_seal.h): container i holds the envelopes of proof_lists[i] and, when `metadata` is given, the entries of the dict
+    metadata[i] (str -> bytes) in dict order; the containers are framed and their digests computed on the GPU.  Returns a list of bytes.
+    errors="raise": for the first container that the reference's own creation refuses (an empty list, an envelope that Proof::from_bytes
+    refuses) the host function runs on it and raises the reference's ValueError / ProofFormatError; a container that
+    CompositeProof::from_bytes would not read back (too many items, a key or value beyond its limit, more than 4 MiB) raises ValueError.
+    errors="none": those places hold None."""
+    import ctypes
+    import numpy as np
+    from . import _native
+    if errors not in ("raise", "none"):
+        raise ValueError("errors must be 'raise' or 'none'")
+    lists = [[bytes(p) for p in lst] for lst in proof_lists]
+    n = len(lists)
+    if metadata is not None and len(metadata) != n:
+        raise ValueError("metadata must hold one dict per container")
+    if n == 0:
+        return []
+    L = _native.lib()
+    if not hasattr(L, "libzkp_seal_composites"):
+        raise _native.NativeError("this build of libzkp_hip.so has no libzkp_seal_composites")
+    envs = [p for lst in lists for p in lst]
+    env_blob = np.frombuffer(b"".join(envs) or b"\0", dtype=np.uint8)
+    env_off, first = seal_offsets([len(p) for p in envs]), seal_offsets([len(lst) for lst in lists])
+    vp = ctypes.c_void_p
+    meta_blob = meta_off = None
+    if metadata is not None:
+        wires = [_metadata_wire(m) for m in metadata]
+        meta_blob, meta_off = np.frombuffer(b"".join(wires) or b"\0", dtype=np.uint8), seal_offsets([len(w) for w in wires])
+    ptr = lambda a: None if a is None else a.ctypes.data_as(vp)  # noqa: E731
+    out_off, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+    cap = int(env_off[-1]) + 4 * len(envs) + (int(meta_off[-1]) if meta_off is not None else 0) + 44 * n          # an upper bound: every container sealed
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    _native.check(L.libzkp_seal_composites(n, ptr(env_blob), ptr(env_off), len(envs), ptr(first), ptr(meta_blob), ptr(meta_off), ptr(out), cap, ptr(out_off), ptr(status)),
+                  "libzkp_seal_composites")
+    if errors == "raise":
+        for i in np.flatnonzero(status != _native.SEAL_SEALED):
+            i = int(i)
+            if status[i] == _native.SEAL_REFUSED:
+                create_composite_proof(lists[i])
+            raise ValueError("composite proof %d would not be read back: %s" % (i, _unreadable_reason(lists[i], metadata[i] if metadata is not None else {})))
+    raw = out[:int(out_off[-1])].tobytes()
+    return [raw[int(out_off[i]):int(out_off[i + 1])] if status[i] == _native.SEAL_SEALED else None for i in range(n)]
+
+
 def extract_proof_metadata(composite_bytes):
     return parse_composite(composite_bytes)[1]
 

@@ -60,6 +60,40 @@ inline bool cp_utf8_ok(const uint8_t* s, uint32_t n) {
     return true;
 }
 
+// Proof::from_bytes' verdict on an inner proof of n bytes, from n and its ten header bytes at p (proof/mod.rs:38-85).  p is read only when
+// n >= VE_HEADER.  One copy for the walk below and for the sealing plan (composite_seal.h).
+inline bool cp_proof_accepts(const uint8_t* p, uint64_t n) {
+    if (n > VE_MAX_TOTAL || n < VE_HEADER) return false;
+    const uint64_t plen = ve_le(p + 2, 4), clen = ve_le(p + 6, 4);
+    return !(plen > VE_MAX_PAYLOAD || clen > VE_MAX_COMMITMENT || n != VE_HEADER + plen + clen);
+}
+// One metadata entry of c[0 .. len) at offset `at`, as from_bytes judges it: the key's length and UTF-8, the value's length, and that
+// every field lies inside len.  On true E describes it and `at` is behind it.  One copy for the walk and the sealing plan.
+struct CpMetaEntry { uint32_t at, klen, index, bytes; };
+inline bool cp_meta_entry(const uint8_t* c, uint64_t len, uint64_t& at, uint32_t index, CpMetaEntry& E) {
+    if (at + 4 > len) return false;
+    const uint64_t kl = ve_le(c + at, 4);
+    if (kl > CP_MAX_KEY || at + 4 + kl > len) return false;
+    if (!cp_utf8_ok(c + at + 4, (uint32_t)kl)) return false;
+    if (at + 4 + kl + 4 > len) return false;
+    const uint64_t vl = ve_le(c + at + 4 + kl, 4);
+    if (vl > CP_MAX_VALUE || at + 8 + kl + vl > len) return false;
+    E = CpMetaEntry{(uint32_t)at, (uint32_t)kl, index, (uint32_t)(8 + kl + vl)};
+    at += 8 + kl + vl;
+    return true;
+}
+// hash order: keys ascending bytewise (a key that is a prefix of another comes first); equal keys in the order they were written
+inline void cp_meta_sort(const uint8_t* c, std::vector<CpMetaEntry>& entries) {
+    std::sort(entries.begin(), entries.end(), [&](const CpMetaEntry& a, const CpMetaEntry& b) {
+        const uint32_t m = a.klen < b.klen ? a.klen : b.klen;
+        const int d = m ? memcmp(c + a.at + 4, c + b.at + 4, m) : 0;
+        if (d) return d < 0;
+        if (a.klen != b.klen) return a.klen < b.klen;
+        return a.index < b.index;
+    });
+}
+inline bool cp_meta_same_key(const uint8_t* c, const CpMetaEntry& a, const CpMetaEntry& b) { return a.klen == b.klen && memcmp(c + a.at + 4, c + b.at + 4, a.klen) == 0; }
+
 // Container [lo, hi) of a blob whose readable bytes are [blob_lo, blob_hi) (offsets into `blob`).  Appends the hashed metadata entries'
 // offsets to `order`.  Reads the length fields, the ten header bytes of every inner proof and the metadata keys, nothing else.
 inline CompWalk comp_walk(const uint8_t* blob, uint64_t lo, uint64_t hi, uint64_t blob_lo, uint64_t blob_hi, std::vector<uint32_t>& order) {
@@ -76,37 +110,22 @@ inline CompWalk comp_walk(const uint8_t* blob, uint64_t lo, uint64_t hi, uint64_
         if (at + 4 > len) return W;
         const uint64_t n = ve_le(c + at, 4); at += 4;
         if (at + n > len) return W;
-        if (n > VE_MAX_TOTAL || n < VE_HEADER) return W;            // Proof::from_bytes (proof/mod.rs:38-85)
-        const uint64_t plen = ve_le(c + at + 2, 4), clen = ve_le(c + at + 6, 4);
-        if (plen > VE_MAX_PAYLOAD || clen > VE_MAX_COMMITMENT || n != VE_HEADER + plen + clen) return W;
+        if (!cp_proof_accepts(c + at, n)) return W;                 // Proof::from_bytes (proof/mod.rs:38-85)
         at += n; proof_bytes += n;
     }
-    struct Entry { uint32_t at, klen, index, bytes; };
-    std::vector<Entry> entries; entries.reserve(nmeta);
+    std::vector<CpMetaEntry> entries; entries.reserve(nmeta);
     for (uint64_t k = 0; k < nmeta; k++) {
-        if (at + 4 > len) return W;
-        const uint64_t kl = ve_le(c + at, 4);
-        if (kl > CP_MAX_KEY || at + 4 + kl > len) return W;
-        if (!cp_utf8_ok(c + at + 4, (uint32_t)kl)) return W;
-        if (at + 4 + kl + 4 > len) return W;
-        const uint64_t vl = ve_le(c + at + 4 + kl, 4);
-        if (vl > CP_MAX_VALUE || at + 8 + kl + vl > len) return W;
-        entries.push_back({(uint32_t)at, (uint32_t)kl, (uint32_t)k, (uint32_t)(8 + kl + vl)});
-        at += 8 + kl + vl;
+        CpMetaEntry e;
+        if (!cp_meta_entry(c, len, at, (uint32_t)k, e)) return W;
+        entries.push_back(e);
     }
     if (at + CP_DIGEST_BYTES != len) return W;                      // digest missing, or bytes behind it
     // hash order: keys ascending bytewise (a key that is a prefix of another comes first); of equal keys the last one stands
-    std::sort(entries.begin(), entries.end(), [&](const Entry& a, const Entry& b) {
-        const uint32_t m = a.klen < b.klen ? a.klen : b.klen;
-        const int d = m ? memcmp(c + a.at + 4, c + b.at + 4, m) : 0;
-        if (d) return d < 0;
-        if (a.klen != b.klen) return a.klen < b.klen;
-        return a.index < b.index;
-    });
+    cp_meta_sort(c, entries);
     uint64_t meta_bytes = 0; uint32_t kept = 0;
     for (size_t k = 0; k < entries.size(); k++) {
-        const Entry& e = entries[k];
-        if (k + 1 < entries.size() && entries[k + 1].klen == e.klen && memcmp(c + e.at + 4, c + entries[k + 1].at + 4, e.klen) == 0) continue;
+        const CpMetaEntry& e = entries[k];
+        if (k + 1 < entries.size() && cp_meta_same_key(c, e, entries[k + 1])) continue;
         order.push_back(e.at); meta_bytes += e.bytes; kept++;
     }
     W.ok = 1; W.nproofs = (uint32_t)nproofs; W.nmeta = kept; W.digest_at = (uint32_t)at; W.proof_bytes = proof_bytes;

@@ -41,10 +41,12 @@
 #include "verify_shards.h"
 #include "venv_steps.h"
 #include "composite_steps.h"
+#include "composite_seal.h"
 #include "vst_steps.h"
 #include "../../include/libzkp_hip_verify.h"
 #include "../../include/libzkp_hip_bp_localise.h"
 #include "../../include/libzkp_hip_composites.h"
+#include "../../include/libzkp_hip_seal.h"
 
 // ================================================================================================ kernels
 
@@ -360,6 +362,8 @@ struct Device {
     struct BpLocaliseCounter { double ms = 0; uint64_t failed_checks = 0, segment_checks = 0, jobs_again = 0; } bp_localise;
     // zkp_hip_composites_counters (libzkp_hip_composites.h): what zkp_hip_verify_composites did on this shard (CompTally)
     struct CompositesCounter { double ms = 0; uint64_t composites = 0, malformed = 0, envelopes = 0; } composites;
+    // libzkp_seal_counters (libzkp_hip_seal.h): what libzkp_seal_composites / _batch did on this shard (SealTally)
+    struct SealCounter { double ms = 0; uint64_t containers = 0, sealed = 0, envelopes = 0, bytes = 0; } seal;
     // zkp_stmt_counters (libzkp_hip_statements.h): what zkp_stmt_verify / _device did on this shard (StmtTally)
     struct StatementsCounter { double ms = 0; uint64_t envelopes = 0, refused_envelope = 0, refused_statement = 0, refused_proof = 0; } statements;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
@@ -1255,6 +1259,7 @@ void zkp_hip_shutdown(void) try {
         d->bp_localise = Device::BpLocaliseCounter();
         d->composites = Device::CompositesCounter();
         d->statements = Device::StatementsCounter();
+        d->seal = Device::SealCounter();
         d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
@@ -1398,3 +1403,4 @@ int zkp_hip_prove_consistency_batch(uint64_t n, const uint64_t* data, const uint
 }  // extern "C"
 
 #include "batch_impl.inc"
+#include "composite_seal_impl.inc"
