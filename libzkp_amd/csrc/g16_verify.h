@@ -18,6 +18,9 @@ struct G16Vk {
     uint32_t n_ic;                 // gamma_abc_g1 length (1 + public inputs)
     const uint32_t* ic;            // [n_ic][20] affine points, Montgomery limbs
     const uint32_t* ic_table;      // optional [n_ic][G16V_NWIN windows][G16V_NENT entries][20]: entry e of window w = (e + 1) * 2^(WBITS w) * IC_i (affine)
+                                   // Entries are read as CARRIED coordinates BELOW 2p (limbs 0..8 < 2^26): what k_g16_build_table's plain form stores, an
+                                   // fq_mul output per coordinate (tests/test_fq_bounds.py: CANON).  That is inside "safe" (< 4p), the class fq_neg and
+                                   // jac_madd take in g16_ic_mul below; tests/test_gpu_devtier_g16.py holds every stored entry to it.
 };
 
 ZKP_HD inline uint32_t ld_u32_le(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }

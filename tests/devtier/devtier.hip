@@ -608,3 +608,6 @@ int devtier_fp(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const u
 int devtier_ge(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, int on_device) { return run_family<GeCase>(op, n, a, b, c, out, on_device); }
 int devtier_point(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, int on_device) { return run_family<PointCase>(op, n, a, b, c, out, on_device); }
 }
+
+// the Groth16 key tables, recodings and their join (entry points of their own)
+#include "devtier_g16.h"

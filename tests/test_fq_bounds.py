@@ -4,7 +4,9 @@ no 64-bit column sum overflows, every borrowed-multiple subtraction has a covere
 to the next iteration is "safe" again (no GPU).
 
 A tracked value is (limbs, val): inclusive upper bounds of the ten limbs and of the integer value, in units of p/1000."""
-P = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
+from fractions import Fraction
+
+P =0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
 R_OVER_P = (1 << 260) * 1000 // P            # 84.6 (x1000)
 PL = [(P >> (26 * i)) & 0x3FFFFFF if i < 9 else P >> 234 for i in range(10)]
 M26 = (1 << 26) - 1
@@ -231,6 +233,10 @@ LOOSE4_LIMB = (1 << 30) - 1               # inclusive limb bound of 4p - Y1 (fq9
 # ZZ, ZZZ < 3 covers the converted accumulator a chunk starts from
 G1_MMADD9_BOUNDS = {"X": 8, "Y": 3, "ZZ": 3, "ZZZ": 3, "qx": 4, "qy": 4}
 G2_MMADD9_BOUNDS = {"X": (104, 10), "Y": (4, 1), "ZZ": (3, 1), "ZZZ": (3, 1), "q": (3, 1)}
+# a packed G1 key-table coordinate (k_g16_build_table), exclusive, in units of p: an fq_mul output of safe operands (< 4p each: below
+# 16 p^2 / 2^260 + p) doubled by fq9_from_fq; test_g1_mmadd9_is_closed_over_its_value_bounds places it, tests/devtier_g16_cases.py holds
+# every built entry to it
+KEY_ENTRY_BOUND = 2 * (Fraction(16 * P, 1 << 260) + 1)
 
 
 def header_constants9():
@@ -305,7 +311,7 @@ def test_g1_mmadd9_is_closed_over_its_value_bounds():
     # key-table entries (k_g16_build_table): an affine coordinate is an fq_mul output of safe operands (< 4p each: < 16 p / 84.6 + p
     # = 1.19 p in ten-limb form), doubled by fq9_from_fq: < 2.4 p < 2^255 -- so the nine-limb integer fits the eight packed words of
     # fq9_pack8 (its top limb stays below 2^24), and after fq9_unpack8 it is inside the entry bound above
-    entry = 2 * (F(16 * P, 1 << 260) + 1)
+    entry = KEY_ENTRY_BOUND
     assert entry < F(24, 10) and entry * P < 1 << 255 and entry < qx
 
 
