@@ -23,7 +23,7 @@ from .composite import (  # noqa: F401
     verify_composite_proofs, verify_composites_counters, create_composite_proofs,
 )
 from ._native import NativeError  # noqa: F401
-from .api import generator_table_info, groth16_verify_counters, batch_self_check_counters, verify_fanout_counters, verify_envelopes, verify_mixed_counters, bp_verify_counters, verify_ops, verify_statements_counters, process_ops_sealed, seal_counters  # noqa: F401  (extensions of this backend, not among the reference's names above)
+from .api import generator_table_info, groth16_verify_counters, batch_self_check_counters, verify_fanout_counters, verify_envelopes, verify_mixed_counters, bp_verify_counters, verify_ops, verify_statements_counters, process_ops_sealed, seal_counters, check_key, key_check_counters  # noqa: F401  (extensions of this backend, not among the reference's names above)
 
 __all__ = [
     "prove_range", "prove_range_with_bits", "prove_threshold_with_bits", "prove_range_batch", "verify_range", "verify_range_batch", "verify_threshold", "verify_threshold_batch", "verify_improvement", "verify_improvement_batch", "verify_consistency", "verify_consistency_batch", "verify_equality", "verify_equality_with_commitment",
@@ -41,6 +41,6 @@ __all__ = [
     "NativeError", "ZkpBackendError", "shutdown",
     "generator_table_info", "groth16_verify_counters", "batch_self_check_counters", "verify_fanout_counters", "verify_envelopes", "verify_mixed_counters", "bp_verify_counters",
     "verify_composite_proofs", "verify_composites_counters", "verify_ops", "verify_statements_counters",
-    "create_composite_proofs", "process_ops_sealed", "seal_counters",
+    "create_composite_proofs", "process_ops_sealed", "seal_counters", "check_key", "key_check_counters",
     "clear_cache", "get_cache_stats", "get_performance_metrics", "prove_range_cached", "prove_threshold_optimized",
 ]

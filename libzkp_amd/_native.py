@@ -40,6 +40,10 @@ STMT_ACCEPTED, STMT_ENVELOPE, STMT_STATEMENT, STMT_PROOF = 0, 1, 2, 3      # ZKP
 # symbols declared in include/libzkp_hip_seal.h (checked by tests/test_abi_seal.py); none of them is a zkp_* name
 EXPORTS_SEAL = ("libzkp_seal_composites", "libzkp_seal_batch", "libzkp_seal_counters")
 SEAL_FAILED_OP, SEAL_SEALED, SEAL_REFUSED, SEAL_UNREADABLE = 0, 1, 2, 3      # LIBZKP_SEAL_*: the status of a container
+# symbols declared in include/libzkp_hip_keycheck.h (checked by tests/test_abi_keycheck.py); neither a zkp_* nor a libzkp_* name
+EXPORTS_KEYCHECK = ("zkpkeycheck_key", "zkpkeycheck_counters")
+KEYCHECK_POINTS, KEYCHECK_TWINS, KEYCHECK_TABLES = 1, 2, 4                                     # ZKP_KEYCHECK_*: the stages of a key check
+KEYCHECK_SOUND, KEYCHECK_FAILED_FORMAT, KEYCHECK_FAILED_SUBGROUP, KEYCHECK_FAILED_TWINS, KEYCHECK_FAILED_TABLES = 0, 1, 2, 3, 4      # report.verdict
 
 _lib = None
 
@@ -48,6 +52,17 @@ class Op(ctypes.Structure):
     """zkp_hip_op of include/libzkp_hip.h"""
     _fields_ = [("kind", ctypes.c_uint32), ("count", ctypes.c_uint32), ("a", ctypes.c_uint64), ("b", ctypes.c_uint64), ("c", ctypes.c_uint64),
                 ("list_off", ctypes.c_uint64)]
+
+
+class KeyCheckReport(ctypes.Structure):
+    """zkp_keycheck_report of include/libzkp_hip_keycheck.h"""
+    _fields_ = [("format", ctypes.c_uint32), ("verdict", ctypes.c_uint32), ("stages_run", ctypes.c_uint32),
+                ("g2_checked", ctypes.c_uint32), ("g2_outside", ctypes.c_uint32), ("g2_first_outside", ctypes.c_int32),
+                ("twins_checked", ctypes.c_uint32), ("twin_inf_mismatches", ctypes.c_uint32), ("twins_query_ok", ctypes.c_int32), ("twins_beta_delta_ok", ctypes.c_int32),
+                ("table_first_which", ctypes.c_int32), ("table_first_slot", ctypes.c_uint32), ("table_first_window", ctypes.c_uint32), ("table_first_entry", ctypes.c_uint32),
+                ("table_bad_pairs", ctypes.c_uint32),
+                ("table_entries_g1", ctypes.c_uint64), ("table_entries_g2", ctypes.c_uint64), ("table_entries_vk", ctypes.c_uint64),
+                ("ms_points", ctypes.c_double), ("ms_twins", ctypes.c_double), ("ms_tables", ctypes.c_double), ("message", ctypes.c_char * 160)]
 
 
 OP_RANGE, OP_EQUALITY, OP_THRESHOLD, OP_MEMBERSHIP, OP_IMPROVEMENT, OP_CONSISTENCY = 1, 2, 3, 4, 5, 6
@@ -188,6 +203,11 @@ def lib():
             L.libzkp_seal_batch.restype = ctypes.c_int
             L.libzkp_seal_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
             L.libzkp_seal_counters.restype = ctypes.c_int
+        if hasattr(L, "zkpkeycheck_key"):                   # (an older build loaded through ZKP_HIP_LIB has none; api.check_key then raises)
+            L.zkpkeycheck_key.argtypes = [ctypes.c_int, vp, u64, u32, ctypes.POINTER(KeyCheckReport)]
+            L.zkpkeycheck_key.restype = ctypes.c_int
+            L.zkpkeycheck_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 3 + [ctypes.c_int]
+            L.zkpkeycheck_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

@@ -376,6 +376,51 @@ def install_verifying_key(kind, blob):
         _keys_loaded[kind] = "<installed verifying key>"
 
 
+_KEYCHECK_VERDICTS = ("sound", "format", "subgroup", "twins", "tables")
+_KEYCHECK_TABLES = ("g1", "g2", "vk")
+
+
+def check_key(kind, blob=None, twins=True, tables=None):
+    """The Groth16 key check on the GPU (zkpkeycheck_key, include/libzkp_hip_keycheck.h) of `blob` as a key of circuit `kind` (0 equality,
+    1 membership), either format.  blob=None: this process's key (loaded or generated first, as a verify call would).  Always: format,
+    shape and the G2 points' subgroup membership, what the loader enforces.  twins=True: a proving key's b_g1_query / b_g2_query, beta and
+    delta pairs share their discrete logarithms (a verifying key has none: the two verdicts are None).  tables: every entry of the window
+    tables resident on this shard against the key's points; None means "yes when the blob is the loaded key".
+    Returns the report as a dict; "verdict" is "sound" or the first stage that failed ("format", "subgroup", "twins", "tables")."""
+    if blob is None:
+        _ensure_key(kind, verifier=True)
+        blob = _key_blobs[kind]
+    blob = bytes(blob)
+    if tables is None:
+        tables = kind in _keys_loaded and _key_blobs.get(kind) == blob
+    what = _native.KEYCHECK_POINTS | (_native.KEYCHECK_TWINS if twins else 0) | (_native.KEYCHECK_TABLES if tables else 0)
+    rep = _native.KeyCheckReport()
+    if _native.lib().zkpkeycheck_key(kind, blob, len(blob), what, ctypes.byref(rep)) != 0:
+        raise ZkpBackendError("Key check failed: %s" % _native.last_error())
+    tri = lambda v: None if v < 0 else bool(v)      # noqa: E731
+    first = None if rep.table_first_which < 0 else {"table": _KEYCHECK_TABLES[rep.table_first_which], "slot": int(rep.table_first_slot),
+                                                    "window": int(rep.table_first_window), "entry": int(rep.table_first_entry)}
+    return {"format": ("proving_key", "verifying_key", None)[rep.format], "verdict": _KEYCHECK_VERDICTS[rep.verdict], "sound": rep.verdict == 0,
+            "stages_run": [n for n, bit in (("points", 1), ("twins", 2), ("tables", 4)) if rep.stages_run & bit],
+            "g2_checked": int(rep.g2_checked), "g2_outside": int(rep.g2_outside), "g2_first_outside": None if rep.g2_first_outside < 0 else int(rep.g2_first_outside),
+            "twins_checked": int(rep.twins_checked), "twin_inf_mismatches": int(rep.twin_inf_mismatches),
+            "twins_query_ok": tri(rep.twins_query_ok), "twins_beta_delta_ok": tri(rep.twins_beta_delta_ok),
+            "table_entries": {"g1": int(rep.table_entries_g1), "g2": int(rep.table_entries_g2), "vk": int(rep.table_entries_vk)},
+            "table_bad_pairs": int(rep.table_bad_pairs), "table_first_bad": first,
+            "ms": {"points": float(rep.ms_points), "twins": float(rep.ms_twins), "tables": float(rep.ms_tables)},
+            "message": rep.message.decode("utf-8", "replace")}
+
+
+def key_check_counters(reset=True):
+    """What the key loader's checks and check_key did, summed over the shards since the last reset (zkpkeycheck_counters,
+    include/libzkp_hip_keycheck.h; always counted): {"loads_checked": key loads whose freshly built tables were self-checked,
+    "entries_checked": table entries checked, "refused": keys refused at load or judged unsound by check_key, "ms": host time of the table
+    checks}.  reset=True zeroes the counters."""
+    ms, a, b, c = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().zkpkeycheck_counters(ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), 1 if reset else 0), "zkpkeycheck_counters")
+    return {"loads_checked": int(a.value), "entries_checked": int(b.value), "refused": int(c.value), "ms": float(ms.value)}
+
+
 def snark_commit_value_batch(values):
     v = np.array([_check_u64("value", x) for x in values], dtype=np.uint64)
     if len(v) == 0:

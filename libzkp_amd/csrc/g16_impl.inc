@@ -25,6 +25,7 @@ struct G16Key {
     const uint32_t *init_g1 = nullptr, *init_g2 = nullptr;
     G16Vk vk{}; bool vk_ready = false;        // the verifying key (loaded alone, or the one that leads the proving key file): all the verification entry points read
     uint64_t vk_table_bytes = 0;              // HBM held by vk.ic_table
+    uint8_t digest[32] = {}; bool have_digest = false;      // SHA-256 of the key bytes a successful load read (zkpkeycheck_key: is this the loaded key?)
     bool verifier_only() const { return vk_ready && !loaded; }
     const uint32_t *vm_kconst = nullptr, *vm_lines = nullptr;      // the Fq2 machine's Miller value of (beta, -alpha) and line table of gamma, delta (fq2vm.h)
 };
@@ -209,12 +210,108 @@ void register_tables(G16Key& K, SharedTables e) {
     e.refs = 1; R.v.push_back(e);          // freshly built tables, K their first holder
     K.shared_tables = (int)R.v.size() - 1; K.table_g1 = e.g1; K.table_g2 = e.g2;
 }
+// ---- the key check at load (g16_keycheck.h, DESIGN.md R20)
+// ZKP_HIP_G16_TABLE_FLIP=<g1|g2|vk>:<word index>, read on every load: bit 0 of that word of the named table is flipped between its build and
+// its check (a diagnostic modelled on ZKP_HIP_SELF_CHECK_FLIP).  No effect on tables that are acquired, not built.
+struct KcFlip { int which = -1; uint64_t word = 0; };
+int kc_read_flip(KcFlip& F) {
+    F = KcFlip();
+    const char* e = getenv("ZKP_HIP_G16_TABLE_FLIP");
+    if (!e || !*e) return 0;
+    static const char* names[3] = {"g1:", "g2:", "vk:"};
+    for (int k = 0; k < 3; k++) {
+        if (strncmp(e, names[k], 3)) continue;
+        const char* q = e + 3; char* end = nullptr;
+        if (*q < '0' || *q > '9') break;
+        errno = 0;
+        const unsigned long long v = strtoull(q, &end, 10);
+        if (errno || !end || *end) break;
+        F.which = k; F.word = v;
+        return 0;
+    }
+    return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_G16_TABLE_FLIP must be <g1|g2|vk>:<word index>");
+}
+struct KcLoadOpts { KcFlip flip; bool check = true; };
+int kc_read_load_opts(KcLoadOpts& O) { O.check = env_int("ZKP_HIP_G16_TABLE_CHECK", 1) != 0; return kc_read_flip(O.flip); }
+static const char* const KC_TABLE_NAME[3] = {"G1", "G2", "VK"};
+// what one table check found
+struct KcTableResult { uint64_t entries = 0; uint32_t bad_pairs = 0, bad_entries = 0, slot = 0, win = 0, ent = 0; std::vector<uint32_t> pair_bad; };
+// every entry of the `nslots` slots of `table` against d_bases; waits for the result.  Counts into the shard's keycheck counters.
+int kc_check_table(bool g2, const uint32_t* d_bases, uint32_t nslots, const uint32_t* table, bool msm_form, const G16Radix& rx, KcTableResult& R, bool want_pairs = false) {
+    const auto t0 = std::chrono::steady_clock::now();
+    R = KcTableResult();
+    if (nslots == 0) return 0;
+    DevScope mem;
+    uint32_t *d_pairs = nullptr, *d_out = nullptr;
+    const size_t npairs = (size_t)nslots * rx.nwin;
+    HIP_TRY(mem.alloc(&d_pairs, npairs * 4)); HIP_TRY(mem.alloc(&d_out, KC_OUT_WORDS * 4));
+    HIP_TRY(g16_launch_check_table(g2, d_bases, nslots, table, msm_form, rx, d_pairs, d_out, dev().stream));
+    uint32_t out[KC_OUT_WORDS];
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, dev().stream));
+    if (want_pairs) { R.pair_bad.resize(npairs); HIP_TRY(hipMemcpyAsync(R.pair_bad.data(), d_pairs, npairs * 4, hipMemcpyDeviceToHost, dev().stream)); }
+    HIP_TRY(hipStreamSynchronize(dev().stream));
+    R.entries = (uint64_t)nslots * rx.slot_ent; R.bad_pairs = out[0]; R.bad_entries = out[1];
+    if (R.bad_pairs) { const uint64_t key = (uint64_t)out[3] << 32 | out[2]; R.slot = (uint32_t)(key >> 40); R.win = (uint32_t)(key >> 32) & 0xffu; R.ent = (uint32_t)key; }
+    Device::KeyCheckCounter& C = dev().keycheck;
+    C.entries_checked += R.entries; C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+// a freshly built table: the flip diagnostic when it names this table, then the self-check.  `which`: 0 G1, 1 G2, 2 VK (KC_TABLE_NAME)
+int kc_after_build(int which, const uint32_t* d_bases, uint32_t nslots, uint32_t* table, bool msm_form, const G16Radix& rx, const KcLoadOpts& O) {
+    const bool g2 = which == 1;
+    if (O.flip.which == which) {
+        const uint64_t words = (uint64_t)nslots * rx.slot_ent * g16_table_entry_words(g2, msm_form);
+        if (O.flip.word >= words) return fail(ZKP_HIP_E_ARGUMENT, "ZKP_HIP_G16_TABLE_FLIP: word index beyond the table");
+        g16_launch_flip_word(table, O.flip.word, dev().stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!O.check) return 0;
+    KcTableResult R; int rc;
+    if ((rc = kc_check_table(g2, d_bases, nslots, table, msm_form, rx, R))) return rc;
+    if (!R.bad_pairs) return 0;
+    dev().keycheck.refused++;
+    char msg[200];
+    snprintf(msg, sizeof msg, "Groth16 key tables failed their self-check (%s slot %u window %u, %u inconsistent windows)", KC_TABLE_NAME[which], R.slot, R.win, R.bad_pairs);
+    return fail(ZKP_HIP_E_RUNTIME, msg);
+}
+// the finite G2 points of a key on the GPU, one lane each: ok[i] = 1 inside the prime-order subgroup
+int kc_subgroup_run(const G16G2List& L, std::vector<uint8_t>& ok) {
+    ok.assign(L.pts.size(), 0);
+    if (L.pts.empty()) return 0;
+    static_assert(sizeof(g2_aff) == 160, "40 plain words per G2 point");
+    DevScope mem;
+    uint32_t* d_pts = nullptr; uint8_t* d_ok = nullptr;
+    HIP_TRY(mem.alloc(&d_pts, L.pts.size() * sizeof(g2_aff))); HIP_TRY(mem.alloc(&d_ok, L.pts.size()));
+    HIP_TRY(hipMemcpyAsync(d_pts, L.pts.data(), L.pts.size() * sizeof(g2_aff), hipMemcpyHostToDevice, dev().stream));
+    g16_launch_subgroup(d_pts, (uint32_t)L.pts.size(), d_ok, dev().stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ok.data(), d_ok, ok.size(), hipMemcpyDeviceToHost, dev().stream));
+    HIP_TRY(hipStreamSynchronize(dev().stream));
+    return 0;
+}
+// ark's rule at load (deserialize_uncompressed is Validate::Yes): every finite G2 point of the key file lies in the prime-order subgroup
+int kc_load_subgroup(const G16VkBlob& B, const G16PkBlob* Q) {
+    const G16G2List L = g16_key_g2_points(B, Q);
+    std::vector<uint8_t> ok; int rc;
+    if ((rc = kc_subgroup_run(L, ok))) return rc;
+    for (size_t i = 0; i < ok.size(); i++) {
+        if (ok[i]) continue;
+        dev().keycheck.refused++;
+        char name[48], msg[160]; g16_g2_point_name(name, sizeof name, L.index[i]);
+        snprintf(msg, sizeof msg, "key point %s is not in the prime-order subgroup of G2", name);
+        return fail(ZKP_HIP_E_ARGUMENT, msg);
+    }
+    return 0;
+}
+
+// d_bases_out: the device copy of the bases the builder read (held by K), for the check that follows the build
 template <uint32_t AW, class Pt>
-int build_tables(G16Key& K, const std::vector<Pt>& bases, uint32_t** table, bool msm_form, const G16Radix& rx, bool owned = true) {
+int build_tables(G16Key& K, const std::vector<Pt>& bases, uint32_t** table, bool msm_form, const G16Radix& rx, bool owned = true, const uint32_t** d_bases_out = nullptr) {
     std::vector<uint32_t> flat; flat.reserve(bases.size() * AW);
     for (auto& b : bases) { const uint32_t* w = reinterpret_cast<const uint32_t*>(&b); for (uint32_t k = 0; k < AW; k++) flat.push_back(w[k]); }
     uint32_t* d_bases = nullptr; int rc;
     if ((rc = dev_upload(K, &d_bases, flat))) return rc;
+    if (d_bases_out) *d_bases_out = d_bases;
     const size_t words = bases.size() * (size_t)rx.slot_ent * g16_table_entry_words(AW == 40, msm_form);
     uint32_t* tab = nullptr;
     if (hipMalloc(&tab, words * 4 + 64) != hipSuccess) {
@@ -223,10 +320,10 @@ int build_tables(G16Key& K, const std::vector<Pt>& bases, uint32_t** table, bool
         return fail(ZKP_HIP_E_RUNTIME, msg);
     }
     if (owned) K.allocs.push_back(tab);
+    *table = tab;                                            // (an unowned table is the caller's from here on, whatever follows)
     g16_launch_build_table(AW == 40, d_bases, (uint32_t)bases.size(), tab, dev().stream, msm_form, rx);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(dev().stream));
-    *table = tab;
     return 0;
 }
 
@@ -255,14 +352,16 @@ int load_key_locked(int kind, const uint8_t* pk, uint64_t len) {
     G16Key& K = g16s().key[kind];
     if (K.loaded || K.shared_tables >= 0 || !K.allocs.empty()) release_key(K);
     int rc;
+    const uint64_t checked_before = dev().keycheck.entries_checked;
     try { rc = load_key_body(kind, pk, len); }
     catch (...) { release_key(K); throw; }               // (the ABI's barrier reports it; the registry reference and the blocks are not leaked)
     if (rc) { const std::string keep = t_err; release_key(K); t_err = keep; }      // a failed load leaves no table reference and no allocation behind
+    if (dev().keycheck.entries_checked != checked_before) dev().keycheck.loads_checked++;      // freshly built tables went through the self-check
     return rc;
 }
 // The verifying-key part of a key, shared by both formats: gamma, delta, gamma_abc_g1 and the constant Miller-loop factor of
 // (beta, -alpha), computed once on the host.  Nothing else is needed to verify (g16_verify.h, fq2vm.h, g16_rlc.h).
-int install_verifying_key(G16Key& K, const G16VkBlob& B) {
+int install_verifying_key(G16Key& K, const G16VkBlob& B, const KcLoadOpts& O) {
     int rc;
     K.vk_ready = false;
     std::vector<g1_aff> ic_pts; for (auto& e : B.abc) ic_pts.push_back(e.p);
@@ -274,7 +373,9 @@ int install_verifying_key(G16Key& K, const G16VkBlob& B) {
     // (the prover's table builder) instead of doubling-and-adding
     uint32_t* d_ic_tab = nullptr;
     const G16Radix vrx = g16_radix(G16V_WBITS);
-    if ((rc = build_tables<20>(K, ic_pts, &d_ic_tab, false, vrx))) return rc;
+    const uint32_t* d_ic_bases = nullptr;
+    if ((rc = build_tables<20>(K, ic_pts, &d_ic_tab, false, vrx, true, &d_ic_bases))) return rc;
+    if ((rc = kc_after_build(2, d_ic_bases, (uint32_t)ic_pts.size(), d_ic_tab, false, vrx, O))) return rc;      // (the table is K's: a failed load frees it)
     K.vk_table_bytes = (uint64_t)ic_pts.size() * vrx.slot_ent * g16_table_entry_words(false, false) * 4ull;
     K.vk.gamma = B.gamma_g2.p; K.vk.delta = B.delta_g2.p; K.vk.beta = B.beta_g2.p; K.vk.n_ic = (uint32_t)B.abc.size(); K.vk.ic = d_ic; K.vk.ic_table = d_ic_tab;
     K.vk.ml_alpha_beta = miller_loop(B.beta_g2.p, aff_neg(B.alpha_g1.p));
@@ -297,6 +398,8 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     int rc;
     // parse: ProvingKey { vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 }, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query },
     // or its vk alone: a blob that ends behind gamma_abc_g1 is a verifying key (g16_keyblob.h)
+    KcLoadOpts O;
+    if ((rc = kc_read_load_opts(O))) return rc;
     KeyReader R{pk, len};
     G16VkBlob B; G16PkBlob Q;
     const int format = g16_read_key_prefix(R, B);
@@ -304,9 +407,12 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         return fail(ZKP_HIP_E_ARGUMENT, "malformed proving key or verifying key (expected ark-serialize uncompressed ProvingKey<Bn254>, or its VerifyingKey<Bn254> alone)");
     if (format == G16_BLOB_VERIFYING_KEY) {          // a verifier-only key: no circuit, no MiMC constants, no MSM tables, no registry entry, no layouts
         if (const char* why = g16_check_verifying_key(B, cs.n_inst)) return fail(ZKP_HIP_E_ARGUMENT, why);
-        return install_verifying_key(K, B);
+        if ((rc = kc_load_subgroup(B, nullptr)) || (rc = install_verifying_key(K, B, O))) return rc;
+        sha256_host(K.digest, pk, len); K.have_digest = true;
+        return 0;
     }
     if (const char* why = g16_read_proving_key(R, B, g16_key_shape(cs), Q)) return fail(ZKP_HIP_E_ARGUMENT, why);
+    if ((rc = kc_load_subgroup(B, &Q))) return rc;           // before any table is built or acquired
     // plan (g16_share.h).  ZKP_HIP_G16_SHARE_AB=0 gives every finite b_g1_query point its own slot and table again; it is read here, once
     // per load, and tables are shared only between loads that read the same value.
     const bool share_ab = env_int("ZKP_HIP_G16_SHARE_AB", 1) != 0;
@@ -322,8 +428,15 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
         if ((rc = choose_radix(P.radix_points_g1, P.radix_points_g2, &wb, &uneven))) return rc;
         K.rx = g16_radix(wb, uneven); want.wbits = K.rx.wbits | K.rx.uneven << 8;
         if (!acquire_tables(K, want, false)) {       // the MSM tables: built here
-            if ((rc = build_tables<20>(K, P.bases_g1, &want.g1, true, K.rx, false))) return rc;
-            if ((rc = build_tables<40>(K, P.bases_g2, &want.g2, true, K.rx, false))) { (void)hipFree(want.g1); return rc; }
+            // built, self-checked (kc_after_build), and only then registered: tables that fail are freed here
+            const uint32_t *b1 = nullptr, *b2 = nullptr;
+            if ((rc = build_tables<20>(K, P.bases_g1, &want.g1, true, K.rx, false, &b1)) || (rc = build_tables<40>(K, P.bases_g2, &want.g2, true, K.rx, false, &b2)) ||
+                (rc = kc_after_build(0, b1, (uint32_t)P.bases_g1.size(), want.g1, true, K.rx, O)) || (rc = kc_after_build(1, b2, (uint32_t)P.bases_g2.size(), want.g2, true, K.rx, O))) {
+                (void)hipDeviceSynchronize();
+                if (want.g1) (void)hipFree(want.g1);
+                if (want.g2) (void)hipFree(want.g2);
+                return rc;
+            }
             register_tables(K, want);
         }
     }
@@ -334,11 +447,158 @@ int load_key_body(int kind, const uint8_t* pk, uint64_t len) {
     K.hscal_g1 = P.row_g1; K.hscal_g2 = P.row_g2;
     if ((rc = upload_offset_point(K, false, &K.init_g1)) || (rc = upload_offset_point(K, true, &K.init_g2))) return rc;
     // the verifying key that leads the file; one that cannot verify (gamma or a gamma_abc_g1 point at infinity) leaves a key that only proves
-    if (!g16_check_verifying_key(B, K.n_inst) && (rc = install_verifying_key(K, B))) return rc;
+    if (!g16_check_verifying_key(B, K.n_inst) && (rc = install_verifying_key(K, B, O))) return rc;
+    memcpy(K.digest, want.digest, 32); K.have_digest = true;
     K.loaded = true;
     return 0;
 }
 
+
+// ---- zkpkeycheck_key (include/libzkp_hip_keycheck.h): the stages of a key check on the bound shard
+// fresh bytes from the operating system; a call interrupted by a signal before it read anything is repeated
+int kc_fresh_bytes(uint8_t* buf, size_t n) {
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t r = getrandom(buf + got, n - got, 0);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return fail(ZKP_HIP_E_RUNTIME, "getrandom failed");
+        got += (size_t)r;
+    }
+    return 0;
+}
+bool kc_pairings_equal(const g1_aff& p1, const g2_aff& q1, const g1_aff& p2, const g2_aff& q2) {      // e(p1, q1) == e(p2, q2)
+    return fq12_is_one(final_exponentiation_chain(fq12_mul(miller_loop(q1, p1), miller_loop(q2, aff_neg(p2)))));
+}
+// TWINS: S1 = sum rho_i b_g1_query[i], S2 = sum rho_i b_g2_query[i] on the GPU (a lane per point, then the sum tree), the pairings on the host
+int kc_twins_run(const G16VkBlob& B, const G16PkBlob& Q, zkp_keycheck_report& rep) {
+    const G16Twins T = g16_key_twins(Q);
+    rep.twins_checked = (uint32_t)T.index.size(); rep.twin_inf_mismatches = T.inf_mismatches;
+    if (T.inf_mismatches) { rep.twins_query_ok = 0; return 0; }          // fails the stage before any arithmetic
+    const uint32_t n = (uint32_t)T.index.size();
+    if (n > 65535u) return fail(ZKP_HIP_E_UNSUPPORTED, "too many twins for one sum (16-bit chunk indices)");
+    rep.twins_beta_delta_ok = kc_pairings_equal(Q.beta_g1.p, B.delta_g2.p, Q.delta_g1.p, B.beta_g2.p) ? 1 : 0;
+    if (n == 0) { rep.twins_query_ok = 1; return 0; }
+    std::vector<g1_aff> p1(n); std::vector<g2_aff> p2(n); std::vector<uint8_t> rho(16 * (size_t)n);
+    for (uint32_t k = 0; k < n; k++) { p1[k] = Q.b_g1_query[T.index[k]].p; p2[k] = Q.b_g2_query[T.index[k]].p; }
+    int rc;
+    if ((rc = kc_fresh_bytes(rho.data(), rho.size()))) return rc;
+    static_assert(sizeof(g1_aff) == 80 && sizeof(g2_aff) == 160, "plain affine points: 20 / 40 words");
+    const uint16_t tcb[2] = {0, (uint16_t)n};
+    DevScope mem;
+    uint32_t *d_p1 = nullptr, *d_p2 = nullptr, *d_rho = nullptr, *d_part1 = nullptr, *d_part2 = nullptr, *d_sums = nullptr; uint16_t* d_tcb = nullptr;
+    HIP_TRY(mem.alloc(&d_p1, 80 * (size_t)n)); HIP_TRY(mem.alloc(&d_p2, 160 * (size_t)n)); HIP_TRY(mem.alloc(&d_rho, rho.size()));
+    HIP_TRY(mem.alloc(&d_part1, (size_t)G1_JAC_W * 4 * n)); HIP_TRY(mem.alloc(&d_part2, (size_t)G2_JAC_W * 4 * n));
+    HIP_TRY(mem.alloc(&d_sums, (size_t)(G1_JAC_W + G2_JAC_W) * 4)); HIP_TRY(mem.alloc(&d_tcb, sizeof tcb));
+    hipStream_t st = dev().stream;
+    HIP_TRY(hipMemcpyAsync(d_p1, p1.data(), 80 * (size_t)n, hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(d_p2, p2.data(), 160 * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_rho, rho.data(), rho.size(), hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(d_tcb, tcb, sizeof tcb, hipMemcpyHostToDevice, st));
+    g16_launch_twin_weighted(false, d_p1, d_rho, n, d_part1, st); HIP_TRY(hipGetLastError());
+    g16_launch_twin_weighted(true, d_p2, d_rho, n, d_part2, st); HIP_TRY(hipGetLastError());
+    ReduceView R1{}; R1.rows = 1; R1.ntargets = 1; R1.partial = d_part1; R1.target_chunk_begin = d_tcb;
+    ReduceView R2 = R1; R2.partial = d_part2;
+    g16_launch_sum(false, R1, d_sums, st); HIP_TRY(hipGetLastError());
+    g16_launch_sum(true, R2, d_sums + G1_JAC_W, st); HIP_TRY(hipGetLastError());
+    uint32_t sums[G1_JAC_W + G2_JAC_W];
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));          // (the host vectors above are read by the uploads until here)
+    g1_aff s1; g2_aff s2;
+    const bool f1 = jac_to_aff(s1, ld_g1_jac(sums, 0, 0, 1)), f2 = jac_to_aff(s2, ld_g2_jac(sums + G1_JAC_W, 0, 0, 1));
+    // a sum at infinity pairs to one: the identity then holds exactly when the other sum is at infinity too
+    rep.twins_query_ok = (f1 && f2) ? (kc_pairings_equal(s1, B.beta_g2.p, Q.beta_g1.p, s2) ? 1 : 0) : (f1 == f2 ? 1 : 0);
+    return 0;
+}
+// TABLES: the tables resident on this shard for `kind` against the points of the blob.  The MSM tables of a proving key are laid out by
+// g16_plan_key under the ZKP_HIP_G16_SHARE_AB of now, which must be that of the load (the registry entry of K says which it was).
+int kc_tables_run(int kind, const G16VkBlob& B, const G16PkBlob* Q, const HostR1CS& cs, const uint8_t digest[32], zkp_keycheck_report& rep) {
+    G16Key& K = g16s().key[kind];
+    if (!(K.loaded || K.vk_ready) || !K.have_digest || memcmp(K.digest, digest, 32) || (Q != nullptr) != K.loaded)
+        return fail(ZKP_HIP_E_ARGUMENT, "ZKP_KEYCHECK_TABLES: this is not the key loaded for this circuit on this shard");
+    int rc;
+    // one table: upload the bases the builder read, check, fold into the report
+    auto run = [&](int which, const uint32_t* words, uint32_t nslots, uint32_t aw, const uint32_t* table, bool msm_form, const G16Radix& rx, uint64_t& entries) -> int {
+        DevScope mem; uint32_t* d_bases = nullptr;
+        HIP_TRY(mem.alloc(&d_bases, (size_t)nslots * aw * 4));
+        HIP_TRY(hipMemcpyAsync(d_bases, words, (size_t)nslots * aw * 4, hipMemcpyHostToDevice, dev().stream));
+        KcTableResult R;
+        if (int rcc = kc_check_table(which == 1, d_bases, nslots, table, msm_form, rx, R)) return rcc;      // (waits for the stream: `words` is free again)
+        entries = R.entries;
+        if (R.bad_pairs && rep.table_first_which < 0) { rep.table_first_which = which; rep.table_first_slot = R.slot; rep.table_first_window = R.win; rep.table_first_entry = R.ent; }
+        rep.table_bad_pairs += R.bad_pairs;
+        return 0;
+    };
+    if (Q) {
+        bool share_ab = env_int("ZKP_HIP_G16_SHARE_AB", 1) != 0;
+        if (K.shared_tables >= 0) { TableRegistry& TR = table_registry(); std::lock_guard<std::mutex> lk(TR.mu); share_ab = TR.v[(size_t)K.shared_tables].share_ab; }
+        G16KeyPlan P;
+        if (const char* why = g16_plan_key(P, B, *Q, cs, share_ab)) return fail(ZKP_HIP_E_UNSUPPORTED, why);
+        if ((rc = run(0, reinterpret_cast<const uint32_t*>(P.bases_g1.data()), (uint32_t)P.bases_g1.size(), 20, K.table_g1, true, K.rx, rep.table_entries_g1)) ||
+            (rc = run(1, reinterpret_cast<const uint32_t*>(P.bases_g2.data()), (uint32_t)P.bases_g2.size(), 40, K.table_g2, true, K.rx, rep.table_entries_g2))) return rc;
+    }
+    if (K.vk_ready) {
+        std::vector<g1_aff> ic; for (auto& e : B.abc) ic.push_back(e.p);
+        ic.push_back(B.alpha_g1.p);
+        if ((rc = run(2, reinterpret_cast<const uint32_t*>(ic.data()), (uint32_t)ic.size(), 20, K.vk.ic_table, false, g16_radix(G16V_WBITS), rep.table_entries_vk))) return rc;
+    }
+    return 0;
+}
+int keycheck_locked(int kind, const uint8_t* key, uint64_t len, uint32_t what, zkp_keycheck_report& rep) {
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    memset(&rep, 0, sizeof rep);
+    rep.format = ZKP_KEYCHECK_FORMAT_UNKNOWN; rep.g2_first_outside = -1; rep.twins_query_ok = rep.twins_beta_delta_ok = -1; rep.table_first_which = -1;
+    auto verdict = [&](uint32_t v, const char* msg) { rep.verdict = v; snprintf(rep.message, sizeof rep.message, "%s", msg); dev().keycheck.refused++; return 0; };
+    const HostR1CS cs = kind == G16_EQUALITY ? build_equality_r1cs() : build_membership_r1cs();
+    int rc;
+    // POINTS
+    clk::time_point t0 = clk::now();
+    KeyReader R{key, len};
+    G16VkBlob B; G16PkBlob Q;
+    const int format = g16_read_key_prefix(R, B);
+    if (format == G16_BLOB_MALFORMED)
+        return verdict(ZKP_KEYCHECK_FAILED_FORMAT, "malformed proving key or verifying key (expected ark-serialize uncompressed ProvingKey<Bn254>, or its VerifyingKey<Bn254> alone)");
+    const bool is_pk = format == G16_BLOB_PROVING_KEY;
+    rep.format = is_pk ? ZKP_KEYCHECK_FORMAT_PROVING_KEY : ZKP_KEYCHECK_FORMAT_VERIFYING_KEY;
+    if (const char* why = is_pk ? g16_read_proving_key(R, B, g16_key_shape(cs), Q) : g16_check_verifying_key(B, cs.n_inst)) return verdict(ZKP_KEYCHECK_FAILED_FORMAT, why);
+    {
+        const G16G2List L = g16_key_g2_points(B, is_pk ? &Q : nullptr);
+        std::vector<uint8_t> ok;
+        if ((rc = kc_subgroup_run(L, ok))) return rc;
+        rep.g2_checked = (uint32_t)ok.size();
+        for (size_t i = 0; i < ok.size(); i++) if (!ok[i]) { if (rep.g2_first_outside < 0) rep.g2_first_outside = (int32_t)L.index[i]; rep.g2_outside++; }
+    }
+    rep.ms_points = ms_since(t0);
+    if (rep.g2_outside) {
+        char name[48], msg[160]; g16_g2_point_name(name, sizeof name, (uint32_t)rep.g2_first_outside);
+        snprintf(msg, sizeof msg, "key point %s is not in the prime-order subgroup of G2", name);
+        return verdict(ZKP_KEYCHECK_FAILED_SUBGROUP, msg);
+    }
+    rep.stages_run |= ZKP_KEYCHECK_POINTS;
+    // TWINS (a verifying key has none: the two verdicts stay -1, not applicable)
+    if ((what & ZKP_KEYCHECK_TWINS) && is_pk) {
+        t0 = clk::now();
+        if ((rc = kc_twins_run(B, Q, rep))) return rc;
+        rep.ms_twins = ms_since(t0);
+        if (rep.twin_inf_mismatches) return verdict(ZKP_KEYCHECK_FAILED_TWINS, "b_g1_query and b_g2_query are at infinity at different indices");
+        if (rep.twins_query_ok != 1) return verdict(ZKP_KEYCHECK_FAILED_TWINS, "b_g1_query and b_g2_query do not share their discrete logarithms (e(S1, beta_g2) != e(beta_g1, S2))");
+        if (rep.twins_beta_delta_ok != 1) return verdict(ZKP_KEYCHECK_FAILED_TWINS, "beta and delta do not share their discrete logarithms between G1 and G2 (e(beta_g1, delta_g2) != e(delta_g1, beta_g2))");
+        rep.stages_run |= ZKP_KEYCHECK_TWINS;
+    }
+    // TABLES
+    if (what & ZKP_KEYCHECK_TABLES) {
+        t0 = clk::now();
+        uint8_t digest[32]; sha256_host(digest, key, len);
+        if ((rc = kc_tables_run(kind, B, is_pk ? &Q : nullptr, cs, digest, rep))) return rc;
+        rep.ms_tables = ms_since(t0);
+        if (rep.table_bad_pairs) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "Groth16 key tables failed their check (%s slot %u window %u, %u inconsistent windows)", KC_TABLE_NAME[rep.table_first_which], rep.table_first_slot,
+                     rep.table_first_window, rep.table_bad_pairs);
+            return verdict(ZKP_KEYCHECK_FAILED_TABLES, msg);
+        }
+        rep.stages_run |= ZKP_KEYCHECK_TABLES;
+    }
+    return 0;
+}
 
 // ---- native trusted setup (Groth16::circuit_specific_setup, snark.rs:309-339).  The QAP is evaluated at tau on the host
 // (a few thousand Fr operations); every key point is then scalar * generator, computed on the GPU as a one-slot
@@ -812,6 +1072,33 @@ int zkp_hip_groth16_key_info(int kind, uint32_t* wbits, uint32_t* uneven, uint64
     if (wbits) *wbits = K.rx.wbits;
     if (uneven) *uneven = K.rx.uneven ? 1u : 0u;
     if (table_bytes) *table_bytes = K.table_bytes;
+    return 0;
+} ZKP_API_CATCH_INT
+
+// ---- include/libzkp_hip_keycheck.h
+int zkpkeycheck_key(int kind, const uint8_t* key, uint64_t len, uint32_t what, zkp_keycheck_report* report) try {
+    if (kind != G16_EQUALITY && kind != G16_MEMBERSHIP) return fail(ZKP_HIP_E_ARGUMENT, "unknown circuit kind");
+    if (!key || !report) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    if (what & ~(ZKP_KEYCHECK_POINTS | ZKP_KEYCHECK_TWINS | ZKP_KEYCHECK_TABLES)) return fail(ZKP_HIP_E_ARGUMENT, "unknown ZKP_KEYCHECK_* stage");
+    Bind bind; int rc = bind.open();
+    if (rc) return rc;
+    return keycheck_locked(kind, key, len, what, *report);
+} ZKP_API_CATCH_INT
+
+int zkpkeycheck_counters(double* ms, uint64_t* loads_checked, uint64_t* entries_checked, uint64_t* refused, int reset) try {
+    std::vector<Device*> shards;
+    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
+    Device::KeyCheckCounter T;
+    for (Device* d : shards) {
+        std::lock_guard<std::mutex> dl(d->mu);
+        Device::KeyCheckCounter& C = d->keycheck;
+        T.ms += C.ms; T.loads_checked += C.loads_checked; T.entries_checked += C.entries_checked; T.refused += C.refused;
+        if (reset) C = Device::KeyCheckCounter();
+    }
+    if (ms) *ms = T.ms;
+    if (loads_checked) *loads_checked = T.loads_checked;
+    if (entries_checked) *entries_checked = T.entries_checked;
+    if (refused) *refused = T.refused;
     return 0;
 } ZKP_API_CATCH_INT
 

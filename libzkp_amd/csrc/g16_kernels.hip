@@ -1,6 +1,7 @@
 // Groth16 / BN254 kernels of libzkp_hip (second translation unit; launchers declared in g16_launch.h).
 #include "g16_launch.h"
 #include "msm_kernel.h"
+#include "g16_keycheck.h"
 
 struct G1Msm {      // BN254 G1 key points (Groth16 a / b1 / h / l queries): packed affine table entries, XYZZ accumulator
     static constexpr uint32_t ACC_W = G1_JAC_W, DIG_PER_WORD = 2;
@@ -146,6 +147,40 @@ __global__ void __launch_bounds__(TW, 2) k_g16_build_table(const uint32_t* bases
     }
 }
 
+// The check of those tables (g16_keycheck.h): thread = one entry, blockIdx.y = slot, blockIdx.x * KC_TB + threadIdx.x = the
+// entry's index in the slot's block.  Adjacent lanes take adjacent entries of one window (a window is a multiple of 64 entries at every
+// radix), so a wave's loads of its own entries and of their left neighbours are contiguous (4 KB of G1 entries, 8 KB of G2) and the
+// window's first entry is one address for the whole wave.  The builder's mapping -- a thread per 512-entry segment -- would have given
+// every lane its own 32 KB stride.  Each entry is read three times (as itself, as the right neighbour's `prev`, and entry 0 by its whole
+// window), twice of those from cache.  A bad entry counts its (slot, window) in pair_bad; the first one of a pair counts the pair.
+// G1: 162 VGPRs, three waves per SIMD; G2: 256 VGPRs and 146 AGPRs, one wave per SIMD (held to two it spills 756 bytes per lane).  No
+// scratch, no LDS (profiles/g16_keycheck_resource_usage.md).
+constexpr uint32_t KC_TB = 256;
+template <class F>
+__global__ void __launch_bounds__(KC_TB, sizeof(F) == sizeof(fq) ? 3 : 1) k_g16_check_table(KcTableView V) {
+    const uint32_t t = blockIdx.x * KC_TB + threadIdx.x, slot = blockIdx.y;
+    if (t >= V.rx.slot_ent || slot >= V.nslots) return;
+    uint32_t win, ent; kc_window_of(V.rx, t, win, ent);
+    if (kc_table_entry_ok<F>(V, slot, win, ent)) return;
+    if (atomicAdd(&V.pair_bad[(size_t)slot * V.rx.nwin + win], 1u) == 0) atomicAdd(&V.out[0], 1u);
+    atomicAdd(&V.out[1], 1u);
+    atomicMin(reinterpret_cast<unsigned long long*>(V.out + 2), (unsigned long long)kc_location_key(slot, win, ent));
+}
+// ZKP_HIP_G16_TABLE_FLIP: bit 0 of one word of a freshly built table
+__global__ void k_g16_flip_word(uint32_t* table, uint64_t word) { table[word] ^= 1u; }
+// thread = finite G2 point of a key: r * Q is the identity
+__global__ void __launch_bounds__(TW) k_g16_subgroup(const uint32_t* pts, uint32_t n, uint8_t* ok) {
+    const uint32_t i = blockIdx.x * TW + threadIdx.x;
+    if (i < n) step_kc_subgroup(pts, ok, i);
+}
+// thread = twin i: rho_i * point i, stored as partial i of a one-row sum (k_sum_t adds them)
+template <class F>
+__global__ void __launch_bounds__(TW) k_g16_twin_weighted(const uint32_t* pts, const uint32_t* rho, uint32_t n, uint32_t* partial) {
+    const uint32_t i = blockIdx.x * TW + threadIdx.x;
+    if (i >= n) return;
+    const Jac<F> j = kc_weighted<F>(pts, rho, i);
+    if constexpr (sizeof(F) == sizeof(fq)) st_g1_jac(partial, i, 0, 1, j); else st_g2_jac(partial, i, 0, 1, j);
+}
 
 
 // thread = point: Jacobian sum -> ark-serialize uncompressed affine bytes (key generation output)
@@ -200,6 +235,24 @@ void g16_launch_build_table(bool g2, const uint32_t* bases, uint32_t nslots, uin
     const uint32_t threads = nslots * (rx.slot_ent / seg_len);
     if (!g2) k_g16_build_table<fq, 20><<<(threads + TW - 1) / TW, TW, 0, st>>>(bases, nslots, table, msm_form ? 1u : 0u, rx);
     else k_g16_build_table<fq2, 40><<<(threads + TW - 1) / TW, TW, 0, st>>>(bases, nslots, table, msm_form ? 1u : 0u, rx);
+}
+// pair_bad: [nslots * rx.nwin] words, out: KC_OUT_WORDS words (g16_keycheck.h), both cleared here on `st` ahead of the kernel
+hipError_t g16_launch_check_table(bool g2, const uint32_t* bases, uint32_t nslots, const uint32_t* table, bool msm_form, const G16Radix& rx, uint32_t* pair_bad, uint32_t* out, hipStream_t st) {
+    if (nslots == 0 || nslots > 65535u || rx.nent % 64u || rx.slot_ent == 0) return hipErrorInvalidValue;      // blockIdx.y = slot; a wave stays inside one window
+    hipError_t e;
+    if ((e = hipMemsetAsync(pair_bad, 0, (size_t)nslots * rx.nwin * 4, st)) != hipSuccess || (e = hipMemsetAsync(out, 0, 8, st)) != hipSuccess ||
+        (e = hipMemsetAsync(out + 2, 0xff, 8, st)) != hipSuccess) return e;
+    KcTableView V{table, bases, nslots, msm_form ? 1u : 0u, rx, pair_bad, out};
+    const dim3 grid((rx.slot_ent + KC_TB - 1) / KC_TB, nslots);
+    if (!g2) k_g16_check_table<fq><<<grid, KC_TB, 0, st>>>(V); else k_g16_check_table<fq2><<<grid, KC_TB, 0, st>>>(V);
+    return hipGetLastError();
+}
+void g16_launch_flip_word(uint32_t* table, uint64_t word, hipStream_t st) { k_g16_flip_word<<<1, 1, 0, st>>>(table, word); }
+void g16_launch_subgroup(const uint32_t* pts, uint32_t n, uint8_t* ok, hipStream_t st) { if (n) k_g16_subgroup<<<(n + TW - 1) / TW, TW, 0, st>>>(pts, n, ok); }
+void g16_launch_twin_weighted(bool g2, const uint32_t* pts, const uint32_t* rho, uint32_t n, uint32_t* partial, hipStream_t st) {
+    if (!n) return;
+    if (!g2) k_g16_twin_weighted<fq><<<(n + TW - 1) / TW, TW, 0, st>>>(pts, rho, n, partial);
+    else k_g16_twin_weighted<fq2><<<(n + TW - 1) / TW, TW, 0, st>>>(pts, rho, n, partial);
 }
 uint32_t g16_table_entry_words(bool g2, bool msm_form) { return msm_form ? (g2 ? G2Msm::GATHER_W : G1Msm::GATHER_W) : (g2 ? 40u : 20u); }
 uint32_t g16_msm_rows_per_block(bool) { return 256u; }

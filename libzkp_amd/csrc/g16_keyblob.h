@@ -5,6 +5,7 @@
 // reader goes on from where the prefix ended.  No length table and no flag.  Compiled for the host by tests/emul/emul_g16_keyblob.cpp too.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 #include "bn254_g.h"
@@ -93,6 +94,34 @@ inline const char* g16_read_proving_key(KeyReader& R, const G16VkBlob& vk, const
         return "proving key does not match the circuit shape";
     if (vk.alpha_g1.inf || pk.beta_g1.inf || pk.delta_g1.inf || vk.beta_g2.inf || vk.delta_g2.inf) return "degenerate proving key";
     return nullptr;
+}
+
+// ---- the key check's view of a key (g16_keycheck.h).  The finite G2 points in file order, each with the index a report names it by:
+// 0 beta_g2, 1 gamma_g2, 2 delta_g2, 3 + i b_g2_query[i] (pk == nullptr: a verifying key, the first three only).  These are the points ark's
+// Validate::Yes tests for membership of the prime-order subgroup; G1 has cofactor 1 and needs no such test.
+struct G16G2List { std::vector<uint32_t> index; std::vector<g2_aff> pts; };
+inline G16G2List g16_key_g2_points(const G16VkBlob& vk, const G16PkBlob* pk) {
+    G16G2List L;
+    auto add = [&](uint32_t ix, const G2Pt& p) { if (!p.inf) { L.index.push_back(ix); L.pts.push_back(p.p); } };
+    add(0, vk.beta_g2); add(1, vk.gamma_g2); add(2, vk.delta_g2);
+    if (pk) for (size_t i = 0; i < pk->b_g2_query.size(); i++) add(3u + (uint32_t)i, pk->b_g2_query[i]);
+    return L;
+}
+inline void g16_g2_point_name(char* out, size_t cap, uint32_t index) {
+    static const char* head[3] = {"beta_g2", "gamma_g2", "delta_g2"};
+    if (index < 3) snprintf(out, cap, "%s", head[index]); else snprintf(out, cap, "b_g2_query[%u]", index - 3);
+}
+// The twins of a proving key: the indices at which b_g1_query and b_g2_query are both finite, and how many indices have one of the two at
+// infinity and the other not (a key in which the two vectors do not hold the same scalars)
+struct G16Twins { std::vector<uint32_t> index; uint32_t inf_mismatches = 0; };
+inline G16Twins g16_key_twins(const G16PkBlob& pk) {
+    G16Twins T;
+    const size_t n = pk.b_g1_query.size() < pk.b_g2_query.size() ? pk.b_g1_query.size() : pk.b_g2_query.size();
+    for (size_t i = 0; i < n; i++) {
+        if (pk.b_g1_query[i].inf != pk.b_g2_query[i].inf) T.inf_mismatches++;
+        else if (!pk.b_g1_query[i].inf) T.index.push_back((uint32_t)i);
+    }
+    return T;
 }
 
 }  // namespace zkp

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <cerrno>
 #include <chrono>
 #include <sys/random.h>
 #include "bp_layout.h"
@@ -47,6 +48,7 @@
 #include "../../include/libzkp_hip_bp_localise.h"
 #include "../../include/libzkp_hip_composites.h"
 #include "../../include/libzkp_hip_seal.h"
+#include "../../include/libzkp_hip_keycheck.h"
 
 // ================================================================================================ kernels
 
@@ -366,6 +368,8 @@ struct Device {
     struct SealCounter { double ms = 0; uint64_t containers = 0, sealed = 0, envelopes = 0, bytes = 0; } seal;
     // zkp_stmt_counters (libzkp_hip_statements.h): what zkp_stmt_verify / _device did on this shard (StmtTally)
     struct StatementsCounter { double ms = 0; uint64_t envelopes = 0, refused_envelope = 0, refused_statement = 0, refused_proof = 0; } statements;
+    // zkpkeycheck_counters (libzkp_hip_keycheck.h): the key loader's checks and zkpkeycheck_key on this shard (g16_impl.inc)
+    struct KeyCheckCounter { double ms = 0; uint64_t loads_checked = 0, entries_checked = 0, refused = 0; } keycheck;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -1260,6 +1264,7 @@ void zkp_hip_shutdown(void) try {
         d->composites = Device::CompositesCounter();
         d->statements = Device::StatementsCounter();
         d->seal = Device::SealCounter();
+        d->keycheck = Device::KeyCheckCounter();
         d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
