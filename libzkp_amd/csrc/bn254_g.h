@@ -29,8 +29,9 @@ ZKP_HD inline fq2 f_add(const fq2& a, const fq2& b) { return fq2{fq_add(a.c0, b.
 ZKP_HD inline fq2 f_sub(const fq2& a, const fq2& b) { return fq2{fq_sub(a.c0, b.c0), fq_sub(a.c1, b.c1)}; }
 ZKP_HD inline fq2 f_neg(const fq2& a) { return fq2{fq_neg(a.c0), fq_neg(a.c1)}; }
 ZKP_HD inline fq2 f_dbl(const fq2& a) { return fq2{fq_dbl(a.c0), fq_dbl(a.c1)}; }
-// Karatsuba, u^2 = -1.  Inputs safe (< 4p, carried); the three products take lazily added operands (< 8p, limbs < 2^27);
-// c0 = t0 - t1 + 4p, c1 = t2 - t0 - t1 + 8p are reduced once each.
+// Karatsuba, u^2 = -1.  Inputs carried and < 3p, what every operation of this block returns (tests/test_fq_bounds.py: the Fq2 operations are
+// closed over < 3p and not over < 4p -- f_sq's a0 - a1 + 4p needs a1's top limb within the borrowed 4p's); the three products take lazily
+// added operands (< 6p, limbs < 2^27); c0 = t0 - t1 + 4p, c1 = t2 - t0 - t1 + 8p are reduced once each.
 ZKP_HD inline fq2 f_mul(const fq2& a, const fq2& b) {
     const fq t0 = fq_mul(a.c0, b.c0), t1 = fq_mul(a.c1, b.c1);
     const fq t2 = fq_mul(fq_add_l(a.c0, a.c1), fq_add_l(b.c0, b.c1));

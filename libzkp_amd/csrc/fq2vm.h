@@ -17,14 +17,14 @@ namespace zkp { namespace fq2vm {
 enum Op : uint32_t { NOP, MUL, SQ, ADD, SUB, MULXI, CONJ, MUL0, MUL1, INV, LDG, STG, LDC, MOV, NEG, LDK, STC, T3M, T3P, END };
 constexpr uint32_t BAR = 0x80u, FQ2_W = 20;
 
-// 3a - 2b and 3a + 2b (the output step of a cyclotomic squaring) as one operation each: limb-wise (3a < 12p with limbs < 2^28; 2b safe for the
-// 8p-borrowing subtraction: limbs < 2^27, value < 8p), one weak reduction per coordinate
+// 3a - 2b and 3a + 2b (the output step of a cyclotomic squaring) as one operation each: limb-wise (a, b < 3p: 3a < 9p with limbs < 2^28; 2b is covered by the
+// 8p-borrowing subtraction: limbs < 2^27, value < 6p, top limb below the borrowed 8p's), one weak reduction per coordinate
 ZKP_HD inline fq fq_t3(const fq& a, const fq& b, bool minus) {
     const fq a3 = fq_add_l(fq_dbl_l(a), a), b2 = fq_dbl_l(b);
     return fq_reduce_weak(minus ? fq_sub_k8(a3, b2) : fq_add_l(a3, b2));
 }
 ZKP_HD inline fq2 vm_t3(const fq2& a, const fq2& b, bool minus) { return fq2{fq_t3(a.c0, b.c0, minus), fq_t3(a.c1, b.c1, minus)}; }
-// arithmetic operations: inputs and outputs "safe" in the vocabulary of bn254_fq.h (carried, value < 4p)
+// arithmetic operations: inputs and outputs carried with value < 3p, the class tests/test_fq_bounds.py proves them closed over
 ZKP_HD inline fq2 alu(uint32_t op, const fq2& a, const fq2& b) {
     switch (op) {
     case MUL: return f_mul(a, b);

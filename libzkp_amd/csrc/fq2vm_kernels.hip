@@ -159,6 +159,20 @@ void g16_vm_key_constants(const g2_aff& beta, const g1_aff& neg_alpha, const g2_
     }
 }
 
+// One launch of the machine: `script` (device memory, script_len entries, nregs registers) for envelopes [0, count) of the slot buffer io, four
+// waves per 32 envelopes, the register file in dynamic LDS.  The three verification paths below and the device tier launch through here.
+void g16_vm_launch_script(const G16VmTables& T, const uint16_t* script, uint32_t script_len, uint32_t nregs, uint32_t count, uint32_t* io, const uint32_t* kconst, hipStream_t s) {
+    const uint32_t K = 4;
+    fq2vm::Launch L{{T.code, T.off, K, T.consts}, script, script_len, count, io, 0, kconst};
+    k_fq2vm<<<(count + fq2vm::G - 1) / fq2vm::G, K * 64, (size_t)nregs * fq2vm::FQ2_W * fq2vm::G * 4, s>>>(L);
+}
+// chain: 0 = A, 1 = subgroup, 2 = finish, 3 = B (the index of its script in T.script and of its register count in REGS_K4)
+void g16_vm_launch_chain(const G16VmTables& T, int chain, uint32_t count, uint32_t* io, const uint32_t* kconst, hipStream_t s) {
+    const uint32_t len[4] = {(uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), (uint32_t)(sizeof(fq2vm::SCRIPT_SUBGROUP) / 2),
+                             (uint32_t)(sizeof(fq2vm::SCRIPT_FINISH) / 2), (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER_B) / 2)};
+    g16_vm_launch_script(T, T.script[chain], len[chain], fq2vm::REGS_K4[chain], count, io, kconst, s);
+}
+
 void g16_launch_verify_vm(int kind, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, const G16Vk& vk, const G16VmTables& T, const uint32_t* d_kconst,
                           const uint32_t* d_lines, void* d_scratch, uint8_t* d_ok, uint32_t* d_special, hipStream_t st) {
     if (!n) return;
@@ -168,28 +182,23 @@ void g16_launch_verify_vm(int kind, const uint8_t* d_in, uint64_t stride, const 
     const uint32_t nb = (n + 63) / 64;
     k_g16_public_inputs<<<(n + PI_ENV - 1) / PI_ENV, 64, 0, st>>>(kind, d_in, stride, d_len, n, vk, Lbuf);
     k_g16_pairs_vm<<<nb, 64, 0, st>>>(kind, d_in, stride, d_len, n, vk, Lbuf, io, flags);
-    const uint32_t K = 4, ng = (n + fq2vm::G - 1) / fq2vm::G;
     const size_t pair_words = (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W * n;
-    // chain: 0 = A, 1 = subgroup, 2 = finish, 3 = B (the index of its script in T.script and of its register count in REGS_K4)
-    auto launch = [&](int chain, uint32_t* base, const uint32_t* kconst, uint32_t script_len, hipStream_t s) {
-        fq2vm::Launch L{{T.code, T.off, K, T.consts}, T.script[chain], script_len, n, base, 0, kconst};
-        k_fq2vm<<<ng, K * 64, (size_t)fq2vm::REGS_K4[chain] * fq2vm::FQ2_W * fq2vm::G * 4, s>>>(L);
-    };
+    auto launch = [&](int chain, uint32_t* base, const uint32_t* kconst, hipStream_t s) { g16_vm_launch_chain(T, chain, n, base, kconst, s); };
     // Chain B runs beside chain A on a stream of its own (a workgroup's LDS: A 118 KB, B 115 KB: one per CU, 128 + 128 workgroups per 4096
     // envelopes).  The subgroup check of B (38 KB) only feeds the verdict and starts when chain A is done, beside the final exponentiation
     // (159 KB per workgroup: it cannot share a CU with anything, the subgroup workgroups take the other CUs): launched together with A and
     // B its waves shared the SIMDs of chain B's CUs and stretched B, which the final exponentiation waits for, from 3.4 to 5.2 ms.
     (void)hipEventRecord(T.ev[0], st);
     (void)hipStreamWaitEvent(T.side[0], T.ev[0], 0);
-    launch(3, io + pair_words, d_lines, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER_B) / 2), T.side[0]);
+    launch(3, io + pair_words, d_lines, T.side[0]);
     (void)hipEventRecord(T.ev[1], T.side[0]);
-    launch(0, io, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), st);
+    launch(0, io, nullptr, st);
     (void)hipEventRecord(T.ev[0], st);
     (void)hipStreamWaitEvent(T.side[1], T.ev[0], 0);
-    launch(1, io, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_SUBGROUP) / 2), T.side[1]);
+    launch(1, io, nullptr, T.side[1]);
     (void)hipEventRecord(T.ev[2], T.side[1]);
     (void)hipStreamWaitEvent(st, T.ev[1], 0);
-    launch(2, io, d_kconst, (uint32_t)(sizeof(fq2vm::SCRIPT_FINISH) / 2), st);
+    launch(2, io, d_kconst, st);
     (void)hipStreamWaitEvent(st, T.ev[2], 0);
     k_g16_vm_verdict<<<nb, 64, 0, st>>>(n, io, flags, d_ok, d_special);
 }
@@ -394,11 +403,8 @@ void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const
     auto W = [&](size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
     uint32_t *io = W(Y.io), *cbuf = W(Y.cbuf), *acbuf = W(Y.acbuf), *rho = W(Y.rho), *part = W(Y.part), *scal = W(Y.scal), *pts = W(Y.pts), *iov = W(Y.iov), *sums = W(Y.sums), *prods = W(Y.prods), *counters = W(Y.counters);
     uint8_t* flags = base + Y.flags;
-    const uint32_t nb = (n + 63) / 64, K = 4;
-    auto launch = [&](int chain, uint32_t count, uint32_t* buf, const uint32_t* kconst, uint32_t script_len, hipStream_t s) {
-        fq2vm::Launch L{{T.code, T.off, K, T.consts}, T.script[chain], script_len, count, buf, 0, kconst};
-        k_fq2vm<<<(count + fq2vm::G - 1) / fq2vm::G, K * 64, (size_t)fq2vm::REGS_K4[chain] * fq2vm::FQ2_W * fq2vm::G * 4, s>>>(L);
-    };
+    const uint32_t nb = (n + 63) / 64;
+    auto launch = [&](int chain, uint32_t count, uint32_t* buf, const uint32_t* kconst, hipStream_t s) { g16_vm_launch_chain(T, chain, count, buf, kconst, s); };
     // Streams.  st: parse | weighted points | chain A of the batch | product of its values | x V's value | V's finishing chain | verdict.
     // side[1] / sub: the subgroup chain of every B_j (a single round of chain A: from the parse on, beside the weighted points, which use no
     // LDS; several rounds: after chain A, below).  vq[0] (greatest priority): the scalar sums,
@@ -412,7 +418,7 @@ void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const
     (void)hipEventRecord(T.ev[0], st);
     auto subgroup_chain = [&](hipStream_t q) {
         (void)hipStreamWaitEvent(q, T.ev[0], 0);
-        launch(1, n, io, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_SUBGROUP) / 2), q);
+        launch(1, n, io, nullptr, q);
         (void)hipEventRecord(T.ev[2], q);
     };
     if (!a_first) subgroup_chain(T.side[1]);
@@ -422,19 +428,19 @@ void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const
     k_g16_rlc_fixed<<<2, 256, 0, T.vq[0]>>>(vk, scal, pts);
     (void)hipEventRecord(T.ev[4], T.vq[0]);
     k_g16_rlc_virtual<<<1, 64, 0, T.vq[0]>>>(vk, pts, iov, counters, 0u);
-    launch(0, 1, iov, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), T.vq[0]);
+    launch(0, 1, iov, nullptr, T.vq[0]);
     (void)hipEventRecord(T.ev[1], T.vq[0]);
     k_g16_rlc_mul<<<dim3(nb, 2), 64, 0, st>>>(n, rho, acbuf, flags, io, cbuf);
     (void)hipEventRecord(T.ev[0], st);
-    if (a_first) launch(0, n, io, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), st);
+    if (a_first) launch(0, n, io, nullptr, st);
     (void)hipStreamWaitEvent(T.vq[1], T.ev[0], 0);
     k_g1_sum<<<RLC_SUM_BLOCKS, 256, 0, T.vq[1]>>>(cbuf, n, sums, RLC_SUM_BLOCKS);
     k_g1_sum<<<1, 256, 0, T.vq[1]>>>(sums, RLC_SUM_BLOCKS, pts + 60, 1);
     (void)hipStreamWaitEvent(T.vq[1], T.ev[4], 0);                 // (pts[0] = L_V comes from vq[0])
     k_g16_rlc_virtual<<<1, 64, 0, T.vq[1]>>>(vk, pts, iov, counters, 1u);
-    launch(3, 1, iov + (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W, d_lines, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER_B) / 2), T.vq[1]);
+    launch(3, 1, iov + (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W, d_lines, T.vq[1]);
     (void)hipEventRecord(T.ev[3], T.vq[1]);
-    if (!a_first) launch(0, n, io, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), st);
+    if (!a_first) launch(0, n, io, nullptr, st);
     const uint32_t* fin = io + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W * n;
     uint32_t* fv = iov + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W;
     // Several rounds of chain A: the subgroup chain runs AFTER it and the first product pass, beside the rest of the tail (V's finishing chain: ~4 ms on one CU; the subgroup chain's stream
@@ -448,7 +454,7 @@ void g16_launch_verify_rlc(int kind, const uint8_t* d_in, uint64_t stride, const
     (void)hipStreamWaitEvent(tq, T.ev[1], 0);
     (void)hipStreamWaitEvent(tq, T.ev[3], 0);
     k_fq12_prod<<<1, 64, 0, tq>>>(prods, RLC_PROD_BLOCKS, nullptr, fv, 1, fv);
-    launch(2, 1, iov, d_kconst, (uint32_t)(sizeof(fq2vm::SCRIPT_FINISH) / 2), tq);
+    launch(2, 1, iov, d_kconst, tq);
     if (a_first) { (void)hipEventRecord(T.ev[5], tq); (void)hipStreamWaitEvent(st, T.ev[5], 0); }
     (void)hipStreamWaitEvent(st, T.ev[2], 0);
     k_g16_rlc_verdict<<<nb, 64, 0, st>>>(n, io, flags, iov, d_ok, counters);
@@ -648,11 +654,8 @@ void g16_launch_localise(int kind, const uint8_t* d_in, uint64_t stride, const u
     const uint32_t *io = W(rb, Y.io), *cbuf = W(rb, Y.cbuf), *rho = W(rb, Y.rho);
     const uint8_t* flags = rb + Y.flags;
     uint32_t *status = W(lb, Z.status), *vstate = W(lb, Z.vstate), *scal = W(lb, Z.scal), *pts = W(lb, Z.pts), *iov = W(lb, Z.iov);
-    const uint32_t nseg = g.count, nb = (nseg + 63) / 64, K = 4;
-    auto launch = [&](int chain, uint32_t* buf, const uint32_t* kconst, uint32_t script_len, hipStream_t s) {
-        fq2vm::Launch L{{T.code, T.off, K, T.consts}, T.script[chain], script_len, nseg, buf, 0, kconst};
-        k_fq2vm<<<(nseg + fq2vm::G - 1) / fq2vm::G, K * 64, (size_t)fq2vm::REGS_K4[chain] * fq2vm::FQ2_W * fq2vm::G * 4, s>>>(L);
-    };
+    const uint32_t nseg = g.count, nb = (nseg + 63) / 64;
+    auto launch = [&](int chain, uint32_t* buf, const uint32_t* kconst, hipStream_t s) { g16_vm_launch_chain(T, chain, nseg, buf, kconst, s); };
     (void)hipMemsetAsync(iov, 0, (size_t)fq2vm::N_SLOTS * fq2vm::FQ2_W * 4 * nseg, st);
     k_g16_seg_status<<<nseg, 64, 0, st>>>(n, g, flags, d_ok, status);
     k_g16_seg_terms<<<dim3(nseg, vk.n_ic), 64, 0, st>>>(kind, d_in, stride, d_len, n, g, vk, rho, flags, scal);
@@ -662,12 +665,12 @@ void g16_launch_localise(int kind, const uint8_t* d_in, uint64_t stride, const u
     // chain B of the virtual envelopes beside their chain A, as in g16_launch_verify_vm; no subgroup chain: beta is the key's
     (void)hipEventRecord(T.ev[0], st);
     (void)hipStreamWaitEvent(T.side[0], T.ev[0], 0);
-    launch(3, iov + (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W * nseg, d_lines, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER_B) / 2), T.side[0]);
+    launch(3, iov + (size_t)fq2vm::PAIR_SLOTS * fq2vm::FQ2_W * nseg, d_lines, T.side[0]);
     (void)hipEventRecord(T.ev[1], T.side[0]);
-    launch(0, iov, nullptr, (uint32_t)(sizeof(fq2vm::SCRIPT_MILLER) / 2), st);
+    launch(0, iov, nullptr, st);
     k_fq12_seg_prod<<<nseg, 64, 0, st>>>(io + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W * n, n, flags, g, iov + (size_t)fq2vm::SLOT_F0 * fq2vm::FQ2_W * nseg);
     (void)hipStreamWaitEvent(st, T.ev[1], 0);
-    launch(2, iov, d_kconst, (uint32_t)(sizeof(fq2vm::SCRIPT_FINISH) / 2), st);
+    launch(2, iov, d_kconst, st);
     k_g16_seg_suspects<<<nb, 64, 0, st>>>(nseg, iov, status, vstate, lb + Z.suspect);
 }
 // the suspect segments' envelopes and lengths into (d_in2, d_len2); d_off: g16_loc_offsets of the suspect bytes, in device memory

@@ -21,6 +21,10 @@ struct G16VmTables {
 };
 int g16_vm_upload(G16VmTables& T);
 void g16_vm_free(G16VmTables& T);
+// One launch of the machine on the slot buffer io[slot][20][count].  chain: 0 = A, 1 = subgroup, 2 = finish, 3 = B (its script in T.script, its
+// length and register count from fq2vm_programs.h); the explicit form takes any script in device memory with its register count (chain L).
+void g16_vm_launch_chain(const G16VmTables& T, int chain, uint32_t count, uint32_t* io, const uint32_t* kconst, hipStream_t s);
+void g16_vm_launch_script(const G16VmTables& T, const uint16_t* script, uint32_t script_len, uint32_t nregs, uint32_t count, uint32_t* io, const uint32_t* kconst, hipStream_t s);
 // per key: the machine's Miller value of (beta, -alpha) and the line table of gamma and delta (host computation through the same tables)
 void g16_vm_key_constants(const zkp::g2_aff& beta, const zkp::g1_aff& neg_alpha, const zkp::g2_aff& gamma, const zkp::g2_aff& delta, uint32_t ml[6 * 20], std::vector<uint32_t>& lines);
 size_t g16_vm_scratch_bytes(uint32_t n);

@@ -12,17 +12,13 @@
 #include "../../libzkp_amd/csrc/stark_steps.h"
 #include "../../libzkp_amd/csrc/g16_launch.h"
 #include "../../libzkp_amd/csrc/edg_launch.h"
+#include "devtier_family.h"
 #include <algorithm>
 #include <vector>
 using namespace zkp;
+using namespace devtier;             // Shape, ld, st, run_family: shared with devtier_pairing.hip
 
 namespace {
-
-// words per case of the three operand arrays and of the result; o == 0 marks an unknown op
-struct Shape { uint32_t a, b, c, o; };
-
-template <class T, int N> ZKP_HD inline T ld(const uint32_t* w) { T r; ZKP_UNROLL for (int i = 0; i < N; i++) r.v[i] = w[i]; return r; }
-template <class T, int N> ZKP_HD inline void st(uint32_t* w, const T& x) { ZKP_UNROLL for (int i = 0; i < N; i++) w[i] = x.v[i]; }
 
 // ------------------------------------------------------------------------------------------------ fe25519: ten 25.5-bit limbs
 // result: 10 raw limbs, 8 canonical words (fe_towords), 1 flag
@@ -56,18 +52,20 @@ struct FeCase {
 };
 
 // ------------------------------------------------------------------------------------------------ bn254 fq: ten 26-bit limbs
-// result: 10 raw limbs, 8 canonical words (fq_to_raw: value / 2^260 mod p)
+// result: 10 raw limbs, 8 canonical words (fq_to_raw: value / 2^260 mod p); fq_eq and fq_is_zero return their flag in word 0 (words 1..9 zero)
+// and the canonical words of their first operand
 struct FqCase {
     ZKP_HD static Shape shape(int op) {
         switch (op) {
-            case 0: case 3: case 5: case 6: case 7: return Shape{10, 10, 0, 18};
-            case 1: case 4: case 8: case 9: case 10: case 11: return Shape{10, 0, 0, 18};
+            case 0: case 3: case 5: case 6: case 7: case 12: case 13: case 17: return Shape{10, 10, 0, 18};
+            case 1: case 4: case 8: case 9: case 10: case 11: case 14: case 15: case 18: return Shape{10, 0, 0, 18};
             case 2: return Shape{20, 20, 0, 18};
+            case 16: return Shape{8, 0, 0, 18};
             default: return Shape{0, 0, 0, 0};
         }
     }
     ZKP_HD static void run(int op, const uint32_t* a, const uint32_t* b, const uint32_t*, uint32_t* out) {
-        const fq x = ld<fq, 10>(a);
+        const fq x = op == 16 ? fq_zero() : ld<fq, 10>(a);  // (16 takes eight words, not ten limbs)
         fq r = x;
         switch (op) {
             case 0: r = fq_mul(x, ld<fq, 10>(b)); break;
@@ -81,7 +79,20 @@ struct FqCase {
             case 8: r = fq_reduce_weak(x); break;
             case 9: r = fq_carry(x); break;
             case 10: break;                                 // fq_to_raw of the operand itself
-            default: r = fq_inv(x); break;
+            case 11: r = fq_inv(x); break;
+            // the "safe" (always reduced) operations and the two predicates the verdict kernels use
+            case 12: r = fq_add(x, ld<fq, 10>(b)); break;
+            case 13: r = fq_sub(x, ld<fq, 10>(b)); break;
+            case 14: r = fq_neg(x); break;
+            case 15: r = fq_dbl(x); break;
+            case 16: r = fq_from_raw(a); break;
+            default: {                                      // 17 fq_eq, 18 fq_is_zero
+                const bool flag = op == 17 ? fq_eq(x, ld<fq, 10>(b)) : fq_is_zero(x);
+                ZKP_UNROLL for (int i = 0; i < 10; i++) out[i] = 0;
+                out[0] = flag ? 1u : 0u;
+                fq_to_raw(out + 10, x);
+                return;
+            }
         }
         st<fq, 10>(out, r);
         fq_to_raw(out + 10, r);
@@ -363,46 +374,6 @@ struct GeCase {
         ge_ristretto_encode(out + 40, r);
     }
 };
-
-// ------------------------------------------------------------------------------------------------ one lane per case, 64-lane blocks
-template <class Case> __global__ void __launch_bounds__(64) k_devtier(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out) {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n) return;
-    const Shape s = Case::shape(op);
-    Case::run(op, a + (size_t)i * s.a, b + (size_t)i * s.b, c + (size_t)i * s.c, out + (size_t)i * s.o);
-}
-
-constexpr uint32_t MAX_CASES = 1u << 16;
-
-template <class Case> int run_family(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, int on_device) {
-    const Shape s = Case::shape(op);
-    if (s.o == 0 || n == 0 || n > MAX_CASES || !out || (s.a && !a) || (s.b && !b) || (s.c && !c)) return -1;
-    if (!on_device) {
-        for (uint32_t i = 0; i < n; i++) Case::run(op, a + (size_t)i * s.a, b + (size_t)i * s.b, c + (size_t)i * s.c, out + (size_t)i * s.o);
-        return 0;
-    }
-    const uint32_t* host[3] = {a, b, c};
-    const uint32_t words[3] = {s.a, s.b, s.c};
-    uint32_t* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 3 && e == hipSuccess; k++) {
-        if (!words[k]) continue;
-        const size_t bytes = (size_t)n * words[k] * 4;
-        e = hipMalloc((void**)&dev[k], bytes);
-        if (e == hipSuccess) e = hipMemcpy(dev[k], host[k], bytes, hipMemcpyHostToDevice);
-    }
-    const size_t obytes = (size_t)n * s.o * 4;
-    if (e == hipSuccess) e = hipMalloc((void**)&dev[3], obytes);
-    if (e == hipSuccess) e = hipMemset(dev[3], 0xA5, obytes);      // a lane that stores nothing is seen
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_devtier<Case>, dim3((n + 63) / 64), dim3(64), 0, 0, op, n, dev[0], dev[1], dev[2], dev[3]);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, dev[3], obytes, hipMemcpyDeviceToHost);
-    for (int k = 0; k < 4; k++) if (dev[k]) (void)hipFree(dev[k]);
-    return (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------ the gather and sum kernels, driven directly
 // The launchers are the product's own (g16_launch.h, edg_launch.h, linked from libzkp_hip.so), so the code object under test is the shipped

@@ -313,7 +313,51 @@ def _fq_ops():
         Op("fq", "fq_to_raw", 10, [[carry_in]], lambda a: a, exact=True),
         Op("fq", "fq_inv", 11, [[wide]], lambda a: pow(a, PQ - 2, PQ) * R260 * R260, out_l=FQB.SAFE.l, out_v=4 * PQ),
     ]
+    # the "safe" (always reduced) operations: the operand classes of the comments beside them in bn254_fq.h -- limb sums below 2^31 for
+    # fq_add / fq_dbl, the subtrahend of the 8p-borrowing subtraction for fq_sub / fq_neg -- pushed through the proof's limb-wise steps and
+    # its weak reduction, so every result is held to FQB.SAFE
+    sub_b = _fqcls("sub8-b", FQ_SUB_B[8])
+    words = Cls("words", [2**32 - 1] * 8, W8_OFF)
+    unpacked = V([FQB.M26] * 9 + [(2**256 - 1) >> 234], _milli(1 << 256) + 1)        # fq_unpack of any eight words
+    r2 = V(K["fq_r2_l"], 1000)
+    safe = {"out_l": FQB.SAFE.l, "out_v": FQB.SAFE.val * PQ // 1000 - 1}
+    assert all(FQB.reduce_weak(v).val == FQB.SAFE.val for v in (FQB.add_l(FQ_SUM_IN, FQ_SUM_IN), FQB.sub_k(8, FQ_SUM_IN, FQ_SUB_B[8]), FQB.dbl_l(FQ_SUM_IN),
+                                                                 FQB.sub_k(8, V([0] * 10, 0), FQ_SUB_B[8])))
+    FQB.reduce_weak(FQ_WIDE); FQB.carry(FQB.reduce_weak(FQB.sub_k(8, FQ_SUM_IN, FQB.SAFE)))      # fq_eq: reduce b, subtract, reduce, canonical store
+    ops += [
+        Op("fq", "fq_add", 12, [[sum_in], [sum_in]], lambda a, b: a + b, **safe),
+        Op("fq", "fq_sub", 13, [[sum_in], [sub_b]], lambda a, b: a - b, extra=[(canon(0, FQ_OFF), sub_b.largest())], **safe),
+        Op("fq", "fq_neg", 14, [[sub_b]], lambda a: -a, **safe),
+        Op("fq", "fq_dbl", 15, [[sum_in]], lambda a: 2 * a, **safe),
+        Op("fq", "fq_from_raw", 16, [[words]], lambda a: a * R260, **_fq_out(FQB.mul(unpacked, r2))),
+        Op("fq", "fq_eq", 17, [[sum_in], [wide]], lambda a, b: (a - b) % PQ == 0, kind="flag", extra=_eq_pairs(sum_in, wide)),
+        Op("fq", "fq_is_zero", 18, [[carry_in]], lambda a: a % PQ == 0, kind="flag", extra=[(x,) for k in range(0, 80) for x in _reps(k * PQ, carry_in)]),
+    ]
     return ops
+
+
+def _reps(x, cls):
+    """x as a carried limb vector and again with a unit of 2^26 left in each lower limb in turn (a carry still to come), where the class admits it"""
+    l = canon(x, FQ_OFF)
+    out = [l]
+    for i in range(1, 10):
+        if l[i]:
+            u = list(l); u[i] -= 1; u[i - 1] += 1 << 26
+            out.append(u)
+    return [r for r in out if cls.admits(r)]
+
+
+def _eq_pairs(ca, cb):
+    """what the verdict kernels compare: zero as 0, p, 2p (and 3p - 1, which is not zero), one as 1, p + 1, 2p + 1, and values that differ
+    in the top limb alone"""
+    vals = [(a, b) for a in (0, PQ, 2 * PQ, 3 * PQ - 1) for b in (0, PQ, 2 * PQ)]
+    vals += [(a, b) for a in (1, PQ + 1, 2 * PQ + 1) for b in (1, PQ + 1, 2 * PQ + 1)]
+    one = R260 % PQ                                         # the field's one in Montgomery form, as fq2_one() has it
+    vals += [(one + i * PQ, one + j * PQ) for i in range(3) for j in range(3)]
+    low = (1 << 234) - 12345
+    vals += [(low + (t << 234), low + (u << 234)) for t, u in ((0, 1), (1, 0), (PQ >> 234, 0), (0, PQ >> 234), (5, 5))]
+    vals += [(low + (t << 234), low + (t << 234) + PQ) for t in (0, 1, 77)]
+    return [(x, y) for a, b in vals for x in _reps(a, ca) for y in _reps(b, cb)[:4]]
 
 
 FQ_OPS = _fq_ops()
@@ -324,6 +368,10 @@ def check_fq(op, cases, out):
     for c, o in zip(cases, out):
         raw, words = [int(x) for x in o[:10]], val(o[10:18], W8_OFF)
         ref = op.ref(*values(op, c))
+        if op.kind == "flag":                               # the predicate in word 0, the first operand's canonical words behind it
+            assert raw == [int(ref)] + [0] * 9, (op.id, c, raw)
+            assert words == values(op, c)[0] * RINV260 % PQ, (op.id, c, words)
+            continue
         got = val(raw, FQ_OFF)
         assert (got == ref) if op.exact else (got % PQ == ref % PQ), (op.id, c, raw)
         assert words == ref * RINV260 % PQ, (op.id, c, words)

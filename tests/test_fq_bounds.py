@@ -399,3 +399,90 @@ def test_fr9_constants_and_ntt_growth():
     for a in (R_ - 1, 2 * R_, 5 * R_ + 12345, (1 << 261) - 1, 44 * R_ - 1):
         q = ((a >> 232) * recip) >> 32
         assert q <= a // R_ and a - q * R_ < 23 * R_ // 10
+
+
+# ---- the Fq2 operations of the pairing tower and of the Fq2 machine (bn254_g.h f_*, bn254_pairing.h, fq2vm.h): an Fq2 value is a pair of
+# tracked components.  tests/devtier_pairing_cases.py takes the operand class of its fq2 family from FQ2_CLASS and pushes it through these.
+def f_add2(a, b):
+    return tuple(reduce_weak(add_l(x, y)) for x, y in zip(a, b))
+
+
+def f_sub2(a, b):
+    return tuple(reduce_weak(sub_k(8, x, y)) for x, y in zip(a, b))
+
+
+def f_neg2(a):
+    return f_sub2((V([0] * 10, 0), V([0] * 10, 0)), a)
+
+
+def f_dbl2(a):
+    return tuple(reduce_weak(dbl_l(x)) for x in a)
+
+
+def f_mul(a, b):
+    k = kara(a, b)
+    return reduce_weak(sub_k(4, k[0], k[1])), reduce_weak(sub_k(8, k[2], add_l(k[0], k[1])))
+
+
+def f_sq(a):
+    s = sq_l(a)
+    return reduce_weak(s[0]), reduce_weak(dbl_l(s[1]))
+
+
+def fq_inv(a):
+    """the Fermat ladder: acc <- acc^2 [* base] from one; the bound of acc is iterated to its fixed point"""
+    base, acc = reduce_weak(a), carried(1000)
+    for _ in range(256):
+        s = sq(acc)
+        nxt = carried(max(s.val, mul(s, base).val, acc.val))
+        if nxt.val == acc.val:
+            break
+        acc = nxt
+    else:
+        raise AssertionError("the ladder's bound does not settle")
+    return acc
+
+
+def f_inv(a):
+    d = fq_inv(reduce_weak(add_l(sq(a[0]), sq(a[1]))))
+    return reduce_weak(mul(a[0], d)), f_neg2((reduce_weak(mul(a[1], d)),) * 2)[0]
+
+
+def fq2_mul_fq(a, k):
+    return tuple(reduce_weak(mul(x, k)) for x in a)
+
+
+def fq2_mul_xi(a):
+    a9 = f_add2(f_dbl2(f_dbl2(f_dbl2(a))), a)
+    return reduce_weak(sub_k(8, a9[0], a[1])), reduce_weak(add_l(a9[1], a[0]))
+
+
+def fq_t3(a, b, minus):
+    a3, b2 = add_l(dbl_l(a), a), dbl_l(b)
+    return reduce_weak(sub_k(8, a3, b2) if minus else add_l(a3, b2))
+
+
+def fq2_ops(c):
+    """every arithmetic opcode of fq2vm::alu on operands of the component class c: the bounds of all results"""
+    a = (c, c)
+    outs = [f_mul(a, a), f_sq(a), f_add2(a, a), f_sub2(a, a), fq2_mul_xi(a), (c, f_neg2(a)[1]), fq2_mul_fq(a, c), f_inv(a), f_neg2(a), f_dbl2(a),
+            (fq_t3(c, c, True),) * 2, (fq_t3(c, c, False),) * 2, a]
+    return [x for o in outs for x in o]
+
+
+FQ2_CLASS = SAFE          # the class the Fq2 operations are closed over (below): carried, value < 3p
+
+
+def test_fq2_ops_are_closed_over_safe_and_not_over_4p():
+    """Every Fq2 operation of the tower and of the machine's ALU maps components below 3p (carried) to components below 3p.  Below 4p the set
+    does not close: a carried value just under 4p has a top limb one above that of the borrowed 4p of fq_sub_k4 (f_sq's a0 - a1), and twice it
+    is above the top limb of the borrowed 8p (fq_t3's 3a - 2b) -- the limb-wise differences would wrap.  So < 3p is the contract."""
+    import pytest
+    assert all(o.val <= SAFE.val and o.l == SAFE.l or (o.val <= SAFE.val and max(o.l[:9]) <= M26 and o.l[9] <= SAFE.l[9]) for o in fq2_ops(SAFE))
+    four = carried(4000)
+    assert four.l[9] == C["fq_k4"][9] + 1 and 2 * four.l[9] > C["fq_k8"][9]
+    with pytest.raises(AssertionError, match="subtrahend limb exceeds borrowed 4p"):
+        f_sq((four, four))
+    with pytest.raises(AssertionError, match="subtrahend limb exceeds borrowed 8p"):
+        fq_t3(four, four, True)
+    f_mul((four, four), (four, four))                      # the Karatsuba product alone would take them
