@@ -40,6 +40,7 @@
 #include "bp_steps.h"
 #include "stark_steps.h"
 #include "batch_self_check.h"
+#include "plan_take.h"
 #include "../../include/libzkp_hip.h"
 
 namespace zkp {
@@ -171,7 +172,6 @@ inline void plan_shards(uint64_t n, const zkp_hip_op* ops, uint32_t shards, uint
 // ---- one shard's staging
 constexpr uint32_t LEN_DYN = 0xffffffffu;          // the pack view's len_fixed / dyn_kind values (PackView, batch_impl.inc)
 enum : uint8_t { DYN_NONE = 0, DYN_LEN_STATUS = 1, DYN_LEN_ONLY = 2 };
-inline size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct VariantPlan { uint32_t rows = 0; uint64_t stride = 0, arena = 0; uint32_t row0 = 0; };
 struct StagePlan {
@@ -228,8 +228,7 @@ inline void plan_stage_layout(StagePlan& P, const zkp_hip_op* ops, const uint64_
     for (uint32_t k = 0; k < SC_KINDS; k++) P.var[k].rows = rows[k];
     P.max_total = max_total;
     // ---- layout of the staging image, the arena and the result block
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += pad256(bytes); return o; };
+    PlanTake take;
     P.i_rv = take(8ull * R.rows); P.i_rmin = take(8ull * R.rows); P.i_rmax = take(8ull * R.rows); P.i_rseed = take(32ull * R.rows);
     P.i_ev = take(8ull * E.rows); P.i_eseed = take(32ull * E.rows);
     P.i_mv = take(8ull * M.rows); P.i_msets = take(8ull * G16_MAX_SET * M.rows); P.i_mlen = take(4ull * M.rows); P.i_mseed = take(32ull * M.rows);
@@ -244,14 +243,14 @@ inline void plan_stage_layout(StagePlan& P, const zkp_hip_op* ops, const uint64_
         P.i_thr = take(8ull * T.rows); P.i_var = take(n); P.i_rlen = take(4ull * total); P.i_rop = take(4ull * total); P.i_rok = take(total);
         P.i_oprow = take(4ull * n); P.i_cnt = take(8);
     }
-    P.in_bytes = off;
-    off = 0;
+    P.in_bytes = take.off;
+    take.off = 0;
     for (VariantPlan* v : {&R, &E, &M, &I, &T, &C}) v->arena = take(v->stride * v->rows);
     P.a_dlen = take(4ull * (R.rows + I.rows)); P.a_dst = take(4ull * R.rows);
-    P.arena_bytes = off;
-    off = 0;
+    P.arena_bytes = take.off;
+    take.off = 0;
     P.m_off = take(8ull * (n + 1)); P.m_status = take(4ull * n); P.m_len = take(4ull * n);
-    P.meta_bytes = off;
+    P.meta_bytes = take.off;
 }
 
 // The image of a planned shard into h (P.in_bytes bytes), and the host-side products of the framing.

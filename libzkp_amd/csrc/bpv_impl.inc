@@ -5,16 +5,6 @@
 #include "bpv_plan.h"
 namespace {
 
-// A device buffer that only grows.  What it held is not needed across a growth; the device is idle before the old block is freed.
-struct GrowBuf {
-    uint8_t* p = nullptr; size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
-        HIP_TRY(hipMalloc(&p, bytes)); cap = bytes;
-        return 0;
-    }
-};
 struct VfyState { GrowBuf buf, loc; LayoutSet set; bool ready = false; };      // per shard (Device::vfy); buf: the batch block, loc: localise_bp's two shapes (bpv_plan.h), created by the first batch check that does not stand
 VfyState& vfys() { if (!dev().vfy) dev().vfy = new VfyState(); return *dev().vfy; }
 
@@ -26,7 +16,7 @@ int per_job_pass(const VfyView& C, const DevLayout& D, uint8_t* base, const BpvJ
     bpv_launch_scalars(C, st);
     if (int rc = launch_msm(D, C.M, C.digits, C.partial, st)) return rc;
     bpv_launch_varbase(C, st);
-    ReduceView R{}; R.rows = C.M; R.ntargets = 1; R.partial = C.partial; R.target_chunk_begin = (const uint16_t*)(base + J.tcb); R.enc = (uint32_t*)(base + J.enc);
+    ReduceView R = reduce_view(D, C.M, C.partial, nullptr); R.target_chunk_begin = (const uint16_t*)(base + J.tcb); R.enc = (uint32_t*)(base + J.enc);      // (its own table: J.chunk_table)
     uint32_t* sums = (uint32_t*)(base + J.sums);
     launch_sum_ed(R, sums, st);
     k_encode<<<dim3((C.M + TW - 1) / TW, 1), TW, 0, st>>>(R, sums);
@@ -37,8 +27,7 @@ int per_job_pass(const VfyView& C, const DevLayout& D, uint8_t* base, const BpvJ
 int fixed_base_sum(const DevLayout& D, uint32_t rows, const uint32_t* digits, uint32_t* partial, uint32_t* sums, hipStream_t st) {
     if (D.ntargets != 1) return fail(ZKP_HIP_E_RUNTIME, "Bulletproofs verification: the generator layout has more than one target");
     if (int rc = launch_msm(D, rows, digits, partial, st)) return rc;
-    ReduceView R{}; R.rows = rows; R.ntargets = 1; R.partial = partial; R.target_chunk_begin = D.target_chunk_begin;
-    launch_sum_ed(R, sums, st);
+    launch_sum_ed(reduce_view(D, rows, partial, nullptr), sums, st);
     return 0;
 }
 
@@ -235,7 +224,7 @@ int verify_bp_call(int scheme, uint64_t n, const uint8_t* proofs, uint64_t strid
 
 void bpv_release_all() {
     if (!dev().vfy) return;
-    (void)hipFree(dev().vfy->buf.p); (void)hipFree(dev().vfy->loc.p);      // (a null pointer is accepted)
+    dev().vfy->buf.release(); dev().vfy->loc.release();
     free_set(dev().vfy->set);
     delete dev().vfy; dev().vfy = nullptr;
 }

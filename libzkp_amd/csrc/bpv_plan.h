@@ -23,13 +23,14 @@
 //   the suspects' Mc jobs, compacted (bpv_plan_compact):  suspect count | off 4(count + 1) | the job arrays of Mc jobs
 #pragma once
 #include "bp_verify.h"
+#include "plan_take.h"
 
 namespace zkp {
 
-struct BpvTake { size_t off = 0; size_t operator()(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };      // the running end of a block
+using BpvTake = PlanTake;      // the helper's name before it moved to plan_take.h: host units written against this header keep compiling
 
 struct BpvJobArrays { uint32_t nchunks; uint16_t chunk_table[2]; size_t poff, voff, kind, lgn, bad, pts, scal, zero0, digits, vscal, zero1, partial, sums, enc, tcb; };
-inline BpvJobArrays bpv_plan_jobs(BpvTake& take, uint32_t M, uint32_t nchunks) {
+inline BpvJobArrays bpv_plan_jobs(PlanTake& take, uint32_t M, uint32_t nchunks) {
     BpvJobArrays J{}; J.nchunks = nchunks; J.chunk_table[1] = (uint16_t)(nchunks + VP_NUM);
     J.poff = take(8ull * M); J.voff = take(8ull * M); J.kind = take(M); J.lgn = take(M); J.bad = take(4ull * M);
     J.pts = take((size_t)VP_NUM * GE_W * 4 * M); J.scal = take((size_t)VS_NUM * 32 * M);
@@ -46,7 +47,7 @@ inline void bpv_bind_jobs(VfyView& V, uint8_t* base, const BpvJobArrays& J) {
 
 struct BpvBatchPlan { size_t job_base, env_bad; BpvJobArrays J; size_t rho, fterm, count, rzero1, niels, dig, start, cursor, sorted, bucket, seg, dig1, part1, sum1, result, total; };
 inline BpvBatchPlan bpv_plan_batch(uint64_t n, uint32_t Mw, uint32_t nchunks, bool batch_mode, uint32_t nchunks1) {
-    BpvTake take; BpvBatchPlan P{};
+    PlanTake take; BpvBatchPlan P{};
     P.job_base = take(4 * (n + 1)); P.env_bad = take(4 * n); P.J = bpv_plan_jobs(take, Mw, nchunks);
     if (batch_mode) {
         const size_t N = (size_t)VP_NUM * Mw;
@@ -61,14 +62,14 @@ inline BpvBatchPlan bpv_plan_batch(uint64_t n, uint32_t Mw, uint32_t nchunks, bo
 
 struct BpvSegmentPlan { size_t dig, part, gen, win, suspect, total; };
 inline BpvSegmentPlan bpv_plan_segments(uint32_t count, uint32_t nchunks) {
-    BpvTake take; BpvSegmentPlan P{};
+    PlanTake take; BpvSegmentPlan P{};
     P.dig = take((size_t)NBASE * DIGW * 4 * count); P.part = take((size_t)nchunks * GE_W * 4 * count); P.gen = take((size_t)GE_W * 4 * count);
     P.win = take((size_t)count * RLC_NWIN * GE_W * 4); P.suspect = take(count);
     P.total = take.off; return P;
 }
 struct BpvCompactPlan { size_t suspect, off; BpvJobArrays J; size_t total; };
 inline BpvCompactPlan bpv_plan_compact(uint32_t count, uint32_t Mc, uint32_t nchunks) {
-    BpvTake take; BpvCompactPlan P{};
+    PlanTake take; BpvCompactPlan P{};
     P.suspect = take(count); P.off = take(4ull * (count + 1)); P.J = bpv_plan_jobs(take, Mc, nchunks);
     P.total = take.off; return P;
 }

@@ -32,7 +32,7 @@ struct G16Key {
 // per-shard Groth16 state (Device::g16): both circuits' keys, the MiMC constants, one workspace + side stream per circuit
 // so that equality and membership batches of one mixed batch run concurrently on their own streams
 struct G16Run {
-    void* buf = nullptr; size_t cap = 0; hipStream_t side = nullptr, side2 = nullptr; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    GrowBuf buf; hipStream_t side = nullptr, side2 = nullptr; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // recorded behind the final assembly of the last run on this workspace: the next run (possibly on another stream -- a per-variant
     // call while an asynchronous batch is in flight) waits for it before it overwrites z / digits / partials
     hipEvent_t last = nullptr; bool used = false;
@@ -606,13 +606,7 @@ int keycheck_locked(int kind, const uint8_t* key, uint64_t len, uint32_t what, z
 // (ark-groth16 draws random generators; any generator pair yields a valid key).
 fr tape_fr(const uint32_t seed[8], uint32_t idx, uint32_t slot) { uint32_t w[16]; tape_draw64(w, seed, idx, slot); return fp_from_wide<FrParams>(w); }
 
-// the view k_msm_gather gets of one launch over a key's tables: the radix's table shape, an uploaded layout, the digit row of its slots
-MsmView g16_msm_view(const G16Radix& rx, const DevLayout& D, const uint16_t* slot_scalar, const uint32_t* table, const uint32_t* acc_init, uint32_t rows, const uint32_t* digits, uint32_t* partial) {
-    MsmView m; m.nwin = rx.nwin; m.nent = rx.nent; m.digw = rx.digw; m.slot_ent = rx.slot_ent; m.uneven = rx.uneven; m.rows = rows; m.nslots = D.nslots; m.nchunks = D.nchunks; m.table = table; m.digits = digits;
-    m.slot_base = D.slot_base; m.slot_scalar = slot_scalar; m.slot_nwin = D.slot_nwin; m.chunk_begin = D.chunk_begin; m.chunk_win0 = D.chunk_win0; m.chunk_nwin = D.chunk_nwin; m.partial = partial; m.acc_init = acc_init;
-    m.steps = D.steps; m.chunk_step0 = D.chunk_step0;
-    return m;
-}
+TableShape g16_table_shape(const G16Radix& rx) { return {rx.nwin, rx.nent, rx.digw, rx.slot_ent, rx.uneven}; }      // of a key's tables, for msm_view (zkp_hip.hip)
 
 int gpu_scalar_mults(bool g2, const std::vector<fr>& scalars, std::vector<uint8_t>& out_bytes) {
     const uint32_t rows = (uint32_t)scalars.size(), AW = g2 ? 40 : 20, JW = g2 ? G2_JAC_W : G1_JAC_W, PB = g2 ? 128 : 64;
@@ -637,9 +631,8 @@ int gpu_scalar_mults(bool g2, const std::vector<fr>& scalars, std::vector<uint8_
     const GatherShape shape{rx.nent, rx.slot_ent, rx.uneven ? 1u : 0u, rx.digw};
     if (int rc = upload_layout(lay.d, make_layout_even({SlotList{{0, (uint8_t)rx.nwin}}}, 1), &shape)) return rc;
     g16_launch_build_table(g2, d_base, 1, d_tab, dev().stream, true, rx);
-    g16_launch_msm(g2, g16_msm_view(rx, lay.d, nullptr, d_tab, d_offs, rows, d_dig, d_part), dev().stream);
-    ReduceView R{}; R.rows = rows; R.ntargets = 1; R.partial = d_part; R.target_chunk_begin = lay.d.target_chunk_begin; R.corr = d_offs + JW;
-    g16_launch_sum(g2, R, d_sums, dev().stream);
+    g16_launch_msm(g2, msm_view(g16_table_shape(rx), lay.d, nullptr, d_tab, d_offs, rows, d_dig, d_part), dev().stream);
+    g16_launch_sum(g2, reduce_view(lay.d, rows, d_part, d_offs + JW), d_sums, dev().stream);
     g16_launch_serialize(g2, d_sums, rows, d_out, dev().stream);
     out_bytes.resize((size_t)PB * rows);
     HIP_TRY(hipMemcpyAsync(out_bytes.data(), d_out, out_bytes.size(), hipMemcpyDeviceToHost, dev().stream));
@@ -707,7 +700,7 @@ int generate_key_locked(int kind, const uint8_t* setup_seed, std::vector<uint8_t
 
 int launch_msm_key(bool g2, const G16Radix& rx, const G16Key::Chunking& ch, const uint32_t* table, const uint32_t* acc_init, uint32_t rows, const uint32_t* digits, uint32_t* partial, hipStream_t st) {
     const DevLayout& D = ch.lay;
-    const MsmView m = g16_msm_view(rx, D, ch.scal, table, acc_init, rows, digits, partial);
+    const MsmView m = msm_view(g16_table_shape(rx), D, ch.scal, table, acc_init, rows, digits, partial);
     Device::KProf& K = dev().prof[g2 ? 2 : 1];
     hipEvent_t e1 = nullptr;
     int rc = prof_begin(K, st, &e1);
@@ -723,7 +716,6 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
             uint8_t* d_out, uint64_t stride, hipStream_t st, uint32_t lane = 0) {
     G16Key& K = g16s().key[kind];
     if (!K.loaded) return no_proving_key(K);
-    const uint32_t nsc = g16_nscalars(K.nv, K.m);
     // The steps of one batch in dependency order on three streams, so that the latency-bound ones
     // (QAP, partial sums, the two scalar multiplications) sit beside an MSM instead of between two:
     //   st    : witness, z digits | MSM A,B1 | MSM B2 (G2) -> sum |                       final
@@ -733,24 +725,13 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
     int rc;
     if ((rc = get_chunking(K, false, G16_PART_AB, rows, &c1)) || (rc = get_chunking(K, true, G16_PART_ALL, rows, &c2))) return rc;
     if ((rc = get_chunking(K, false, G16_PART_C, rows, &c1c))) return rc;
-    size_t off = 0;
-    auto sz = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t W = (size_t)32 * rows;
-    const size_t o_z = sz(W * K.nv), o_sd = sz((size_t)K.rx.digw * 4 * rows * nsc), o_rs = sz(W * 2), o_p1 = sz((size_t)c1->lay.nchunks * G1_JAC_W * 4 * rows),
-                 o_p1c = sz((size_t)c1c->lay.nchunks * G1_JAC_W * 4 * rows), o_p2 = sz((size_t)c2->lay.nchunks * G2_JAC_W * 4 * rows),
-                 o_s1 = sz((size_t)3 * G1_JAC_W * 4 * rows), o_s2 = sz((size_t)G2_JAC_W * 4 * rows), o_t1 = sz((size_t)G16_CPARTS * G1_JAC_W * 4 * rows),
-                 o_qe = sz((size_t)3 * 36 * K.m * rows);          // a, b, c: m nine-limb elements per row (g16_steps.h: the lane-per-proof passes)
+    const G16ProvePlan P = g16_prove_plan(rows, K.nv, K.m, K.rx.digw, c1->lay.nchunks, c1c->lay.nchunks, c2->lay.nchunks);      // prover_plan.h
     G16Run& RW = g16s().run[kind][lane & 1u];
-    if (off > RW.cap) {
-        if (RW.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(RW.buf)); RW.buf = nullptr; RW.cap = 0; }
-        HIP_TRY(hipMalloc(&RW.buf, off)); RW.cap = off;
-    }
-    uint8_t* base = (uint8_t*)RW.buf;
+    if ((rc = RW.buf.reserve(P.total))) return rc;
     G16View V{}; V.rx = K.rx; V.rows = rows; V.kind = (uint32_t)kind; V.n_inst = K.n_inst; V.n_wit = K.n_wit; V.nv = K.nv; V.m = K.m;
-    V.value = d_value; V.set_vals = d_set_vals; V.set_len = d_set_len; V.seeds = reinterpret_cast<const uint32_t*>(d_seeds); V.mimc_c = g16s().mimc_dev;
-    V.z = (uint32_t*)(base + o_z); V.sdig = (uint32_t*)(base + o_sd); V.rs = (uint32_t*)(base + o_rs); V.out = d_out; V.stride = stride;
-    V.qap_evals = (uint32_t*)(base + o_qe);
-    uint32_t *p1 = (uint32_t*)(base + o_p1), *p1c = (uint32_t*)(base + o_p1c), *p2 = (uint32_t*)(base + o_p2), *s1 = (uint32_t*)(base + o_s1), *s2 = (uint32_t*)(base + o_s2), *t1 = (uint32_t*)(base + o_t1);
+    V.value = d_value; V.set_vals = d_set_vals; V.set_len = d_set_len; V.seeds = reinterpret_cast<const uint32_t*>(d_seeds); V.mimc_c = g16s().mimc_dev; V.out = d_out; V.stride = stride;
+    const G16ProveBufs B = g16_prove_bind(V, RW.buf.p, P);
+    uint32_t *const p1 = B.p1, *const p1c = B.p1c, *const p2 = B.p2, *const s1 = B.s1, *const s2 = B.s2, *const t1 = B.t1;
     if (!RW.last) {
         for (auto& e : RW.ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&RW.last, hipEventDisableTiming));
@@ -769,7 +750,7 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
     }
     hipStream_t const side = R0.side, side2 = R0.side2;
     hipEvent_t ev_wit = RW.ev[0], ev_ab = RW.ev[1], ev_c = RW.ev[2], ev_cp = RW.ev[3];
-    ReduceView R2{}; R2.rows = rows; R2.ntargets = 1; R2.partial = p2; R2.target_chunk_begin = c2->lay.target_chunk_begin; R2.corr = c2->corr;
+    const ReduceView R2 = reduce_view(c2->lay, rows, p2, c2->corr);
     if (RW.used) HIP_TRY(hipStreamWaitEvent(st, RW.last, 0));
     ZKP_TRACED("k_g16_witness", st, g16_launch_witness(V, st));
     ZKP_TRACED("k_g16_zdigits", st, g16_launch_zdigits(V, st));
@@ -778,14 +759,13 @@ int run_g16(int kind, uint32_t rows, const uint64_t* d_value, const uint64_t* d_
     HIP_TRY(hipStreamWaitEvent(side, ev_wit, 0));
     { TraceMark tm_("k_g16_qap", side); HIP_TRY(g16_launch_qap(V, K.C, side)); }
     if ((rc = launch_msm_key(false, K.rx, *c1c, K.table_g1, K.init_g1, rows, V.sdig, p1c, side))) return rc;
-    ReduceView Rc{}; Rc.rows = rows; Rc.ntargets = 1; Rc.partial = p1c; Rc.target_chunk_begin = c1c->lay.target_chunk_begin; Rc.corr = c1c->corr;
-    ZKP_TRACED("k_sum_t<G1Msm>", side, g16_launch_sum(false, Rc, s1 + (size_t)2 * G1_JAC_W * rows, side));
+    ZKP_TRACED("k_sum_t<G1Msm>", side, g16_launch_sum(false, reduce_view(c1c->lay, rows, p1c, c1c->corr), s1 + (size_t)2 * G1_JAC_W * rows, side));      // s1's third sum
     HIP_TRY(hipEventRecord(ev_c, side));
     // st: A and B1, whose sums the scalar multiplications on side2 wait for, then B2
     if ((rc = launch_msm_key(false, K.rx, *c1, K.table_g1, K.init_g1, rows, V.sdig, p1, st))) return rc;
-    ReduceView Rab{}; Rab.rows = rows; Rab.ntargets = 2; Rab.partial = p1; Rab.target_chunk_begin = c1->lay.target_chunk_begin; Rab.corr = c1->corr;
-    // three slot lists A' | S | B1': A sums the chunks [begin[0], begin[2]), B1 the chunks [begin[1], begin[3]) -- S's chunks go into both
-    if (c1->lay.ntargets == 3) Rab.target_chunk_end = c1->lay.target_chunk_begin + 2;
+    ReduceView Rab = reduce_view(c1->lay, rows, p1, c1->corr);
+    // three slot lists A' | S | B1' are still TWO sums: A over the chunks [begin[0], begin[2]), B1 over [begin[1], begin[3]) -- S's chunks go into both
+    if (c1->lay.ntargets == 3) { Rab.ntargets = 2; Rab.target_chunk_end = c1->lay.target_chunk_begin + 2; }
     // The partial sums of A / B1 feed only the scalar multiplications: they go to side2 with them, so that the G2 MSM -- which needs
     // neither -- follows the G1 MSM directly instead of queueing behind a latency-bound kernel that waits for registers beside the other
     // streams' gather waves (traced: 0.8-3.9 ms for a 0.2 ms kernel).
@@ -856,7 +836,7 @@ void g16_release_all() {
     for (auto& circuit : S->run) for (auto& W : circuit) {
         if (W.side) { (void)hipStreamDestroy(W.side); (void)hipStreamDestroy(W.side2); }
         if (W.last) { for (auto e : W.ev) (void)hipEventDestroy(e); (void)hipEventDestroy(W.last); }
-        if (W.buf) (void)hipFree(W.buf);
+        W.buf.release();
     }
     for (auto& K : S->key) release_key(K);
     if (S->mimc_dev) (void)hipFree(S->mimc_dev);

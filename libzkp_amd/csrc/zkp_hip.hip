@@ -39,6 +39,7 @@
 #include "edg_launch.h"
 #include "batch_self_check.h"
 #include "batch_plan.h"
+#include "prover_plan.h"
 #include "verify_shards.h"
 #include "venv_steps.h"
 #include "composite_steps.h"
@@ -303,6 +304,19 @@ struct DevLayout {
 constexpr int MAXT = 8;
 struct LayoutSet { std::vector<DevLayout> cand; uint32_t max_chunks = 0; };
 
+// A device buffer that only grows: the storage of every workspace of the library (SubBatch::ws, G16Run::buf, VfyState::buf / loc).  What it
+// held is not needed across a growth; the device is idle before the old block is freed.
+struct GrowBuf {
+    uint8_t* p = nullptr; size_t cap = 0;
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        if (p) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
+        HIP_TRY(hipMalloc(&p, bytes)); cap = bytes;
+        return 0;
+    }
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }      // for zkp_hip_shutdown, which has waited for the device (a null pointer is accepted)
+};
+
 struct SubBatch {
     hipStream_t stream = nullptr;
     hipEvent_t start = nullptr, done = nullptr;
@@ -310,8 +324,8 @@ struct SubBatch {
     hipEvent_t side_go = nullptr, side_done = nullptr;
     bool used = false;                             // `done` has been recorded at least once
     bool borrowed = false;                         // stream / side belong to slot 0 (the second slot is a second WORKSPACE on the same streams)
-    void* ws = nullptr;
-    uint32_t capM = 0, capC = 0, cap_chunks = 0;
+    GrowBuf ws;                                    // the prover's workspace (prover_plan.h), large enough for ...
+    uint32_t capM = 0, capC = 0, cap_chunks = 0;   // ... this many jobs and commitment tasks under launches of this many chunks
 };
 constexpr uint32_t NSLOTS = 2;      // device-pointer calls alternate between two sets of streams + workspace, so a caller that
                                     // feeds batches from two of its own streams keeps two batches in flight (bench.py --pipeline 2)
@@ -743,7 +757,7 @@ int init_device() {
 }
 // destroys what a slot holds -- workspace, events, and its streams unless they are slot 0's (`borrowed`) -- and empties it
 void release_sub(SubBatch& sb) {
-    if (sb.ws) (void)hipFree(sb.ws);
+    sb.ws.release();
     for (hipEvent_t e : {sb.start, sb.done, sb.side_go, sb.side_done}) if (e) (void)hipEventDestroy(e);
     if (!sb.borrowed) { if (sb.stream) (void)hipStreamDestroy(sb.stream); if (sb.side) (void)hipStreamDestroy(sb.side); }
     sb = SubBatch();
@@ -933,70 +947,44 @@ struct EnvelopeUpload {
     }
 };
 
-// workspace carving ---------------------------------------------------------------------------------
-struct Ws {
-    JobBuf J; BpView V; CtView T;
-    uint32_t *partial, *ct_partial, *ct_enc, *sums, *ct_sums;
-    uint64_t* ct_off;
-    int* flag;
-};
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+// the prover's workspace (prover_plan.h) --------------------------------------------------------------
+uint32_t ct_chunks() { return dev().ct.max_chunks ? dev().ct.max_chunks : 2; }      // chunks of the commitment launch
 
-// lays the workspace out for M jobs / C commitment tasks starting at base (nullptr = size query)
-size_t carve(uint8_t* base, uint32_t M, uint32_t C, uint32_t max_chunks, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { uint8_t* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    const size_t W = (size_t)8 * 4 * M;   // one scalar slot for all jobs
-    const size_t WD = (size_t)DIGW * 4 * M;   // one digit slot (signed radix-1024 digits of one scalar) for all jobs
-    Ws t{};
-    t.J.v = (uint64_t*)take(8ull * M); t.J.seed_ix = (uint32_t*)take(4ull * M); t.J.proof_ix = (uint32_t*)take(4ull * M);
-    t.J.bl_plus = (int32_t*)take(4ull * M); t.J.bl_minus = (int32_t*)take(4ull * M); t.J.kind = (uint8_t*)take(M);
-    t.J.proof_off = (uint64_t*)take(8ull * M); t.J.commit_off = (uint64_t*)take(8ull * M);
-    t.J.ct_v = (uint64_t*)take(8ull * C); t.J.ct_seed_ix = (uint32_t*)take(4ull * C); t.J.ct_bl_ix = (uint32_t*)take(4ull * C); t.J.ct_off = (uint64_t*)take(8ull * C);
-    t.V.wbits = dev().edg.wbits; t.T.wbits = dev().edg.wbits;      // the device prover's MSMs walk the shard's tables (edg.h)
-    t.V.M = M; t.V.v = t.J.v; t.V.seed_ix = t.J.seed_ix; t.V.proof_ix = t.J.proof_ix; t.V.bl_plus = t.J.bl_plus; t.V.bl_minus = t.J.bl_minus;
-    t.V.kind = t.J.kind; t.V.proof_off = t.J.proof_off; t.V.commit_off = t.J.commit_off;
-    t.V.tape = (uint32_t*)take(W * TAPE_SLOTS); t.V.gamma = (uint32_t*)take(W);
-    t.V.d1 = (uint32_t*)take(WD * P1_NSLOTS); t.V.d2 = (uint32_t*)take(WD * P2_NSLOTS); t.V.dr = (uint32_t*)take(WD * PR_NSLOTS);
-    t.V.yinvpow = (uint32_t*)take(W * 64); t.V.ypq = (uint32_t*)take(W * 32); t.V.r0 = (uint32_t*)take(W * 64); t.V.r1 = (uint32_t*)take(W * 64);
-    t.V.pp = (uint32_t*)take(W * 192); t.V.ab = (uint32_t*)take(W * 256); t.V.gh = (uint32_t*)take(W * 128);
-    t.V.scal = (uint32_t*)take(W * SC_NUM); t.V.tstate = (uint32_t*)take(4ull * 52 * M); t.V.enc = (uint32_t*)take(W * 3);
-    t.partial = (uint32_t*)take((size_t)max_chunks * GE_W * 4 * M);
-    t.sums = (uint32_t*)take((size_t)3 * GE_W * 4 * M);
-    t.T.C = C; t.T.v = t.J.ct_v; t.T.seed_ix = t.J.ct_seed_ix; t.T.bl_ix = t.J.ct_bl_ix;
-    t.T.digits = (uint32_t*)take((size_t)2 * DIGW * 4 * C);
-    t.ct_partial = (uint32_t*)take((size_t)(dev().ct.max_chunks ? dev().ct.max_chunks : 2) * GE_W * 4 * C);
-    t.ct_enc = (uint32_t*)take((size_t)8 * 4 * C);
-    t.ct_sums = (uint32_t*)take((size_t)GE_W * 4 * C);
-    t.ct_off = t.J.ct_off;
-    t.flag = (int*)take(256);
-    if (w) *w = t;
-    return off;
-}
-
+// The slot's workspace holds M jobs and C commitment tasks under the shard's launches.  Growth remembers the largest M, C and chunk count
+// separately: ensure_family of a narrower bit width may raise dev().max_chunks after a workspace exists, and that alone regrows it.
 int ensure_workspace(SubBatch& sb, uint32_t M, uint32_t C) {
-    if (M <= sb.capM && C <= sb.capC && dev().max_chunks <= sb.cap_chunks && sb.ws) return 0;
-    if (sb.ws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(sb.ws)); sb.ws = nullptr; }
+    if (M <= sb.capM && C <= sb.capC && dev().max_chunks <= sb.cap_chunks && sb.ws.p) return 0;
     const uint32_t nm = M > sb.capM ? M : sb.capM, nc = C > sb.capC ? C : sb.capC;
-    const size_t bytes = carve(nullptr, nm, nc, dev().max_chunks, nullptr);
-    HIP_TRY(hipMalloc(&sb.ws, bytes));
-    sb.capM = nm; sb.capC = nc; sb.cap_chunks = dev().max_chunks;
+    if (int rc = sb.ws.reserve(bp_prove_plan(nm, nc, dev().max_chunks, ct_chunks()).total)) return rc;
+    sb.capM = nm; sb.capC = nc; sb.cap_chunks = dev().max_chunks; return 0;
+}
+// ... and bound: planned for pm jobs and pc tasks (>= 1 each), strided by the call's own M and C, on the shard's tables (edg.h)
+int bind_workspace(SubBatch& sb, uint32_t pm, uint32_t pc, uint32_t M, uint32_t C, Ws& w) {
+    if (int rc = ensure_workspace(sb, pm, pc)) return rc;
+    bp_prove_bind(w, sb.ws.p, bp_prove_plan(pm, pc, dev().max_chunks, ct_chunks()), M, C, dev().edg.wbits);
     return 0;
 }
 
+// The views of one launch.  k_msm_gather's: the shape of the tables behind `table` (ed25519: the shard's EdgGeom, Groth16: the key's radix), an
+// uploaded layout, the digit rows of its slots.  k_sum_t's: the layout's targets over its chunk partials; call sites set what differs.
+struct TableShape { uint32_t nwin, nent, digw, slot_ent, uneven; };
+MsmView msm_view(const TableShape& t, const DevLayout& D, const uint16_t* slot_scalar, const uint32_t* table, const uint32_t* acc_init, uint32_t rows, const uint32_t* digits, uint32_t* partial) {
+    MsmView m{}; m.nwin = t.nwin; m.nent = t.nent; m.digw = t.digw; m.slot_ent = t.slot_ent; m.uneven = t.uneven; m.rows = rows; m.nslots = D.nslots; m.nchunks = D.nchunks; m.table = table; m.digits = digits;
+    m.slot_base = D.slot_base; m.slot_scalar = slot_scalar; m.slot_nwin = D.slot_nwin; m.chunk_begin = D.chunk_begin; m.chunk_win0 = D.chunk_win0; m.chunk_nwin = D.chunk_nwin; m.partial = partial; m.acc_init = acc_init;
+    m.steps = D.steps; m.chunk_step0 = D.chunk_step0; return m;
+}
+ReduceView reduce_view(const DevLayout& D, uint32_t rows, const uint32_t* partial, const uint32_t* corr) {
+    ReduceView R{}; R.rows = rows; R.ntargets = D.ntargets; R.partial = partial; R.target_chunk_begin = D.target_chunk_begin; R.corr = corr; return R;
+}
+
 int launch_msm(const DevLayout& D, uint32_t rows, const uint32_t* digits, uint32_t* partial, hipStream_t st) {
-    MsmView m; m.rows = rows; m.nslots = D.nslots; m.nchunks = D.nchunks; m.table = dev().d_edg_table; m.digits = digits;
-    m.slot_base = D.slot_base; m.slot_scalar = nullptr; m.slot_nwin = D.slot_nwin; m.chunk_begin = D.chunk_begin; m.chunk_win0 = D.chunk_win0; m.chunk_nwin = D.chunk_nwin; m.partial = partial; m.acc_init = nullptr;
+    const EdgGeom& g = dev().edg;
+    const MsmView m = msm_view({g.nwin, g.nent, DIGW, g.nwin * g.nent, 0u}, D, nullptr, dev().d_edg_table, nullptr, rows, digits, partial);      // (digit rows keep their 13-word pitch)
     hipEvent_t e1 = nullptr;
     int rc = prof_begin(dev().prof[0], st, &e1);
     if (rc) return rc;
-    {
-        const EdgGeom& g = dev().edg;
-        m.nwin = g.nwin; m.nent = g.nent; m.digw = DIGW; m.slot_ent = g.nwin * g.nent; m.uneven = 0;
-        m.steps = D.steps; m.chunk_step0 = D.chunk_step0;
-        const uint32_t tb = edg_msm_rows_per_block(), ngroups = (rows + tb - 1) / tb, nblocks = D.nchunks * ngroups;
-        ZKP_TRACED("k_msm_gather<EdGather>", st, edg_launch_msm(m, ngroups, nblocks, st, dev().msm_prio_now != 0));
-    }
+    const uint32_t tb = edg_msm_rows_per_block(), ngroups = (rows + tb - 1) / tb, nblocks = D.nchunks * ngroups;
+    ZKP_TRACED("k_msm_gather<EdGather>", st, edg_launch_msm(m, ngroups, nblocks, st, dev().msm_prio_now != 0));
     prof_end(dev().prof[0], st, e1, D.adds_per_row * rows);
     return 0;
 }
@@ -1004,8 +992,7 @@ void launch_sum_ed(const ReduceView& R, uint32_t* sums, hipStream_t st) {
     k_sum_t<EdMsm, ED_SUM_ROWS, ED_SUM_TB><<<dim3((R.rows + ED_SUM_ROWS - 1) / ED_SUM_ROWS, R.ntargets), ED_SUM_TB, 0, st>>>(R, sums);
 }
 int launch_reduce(const DevLayout& D, uint32_t rows, const uint32_t* partial, uint32_t* sums, uint32_t* enc, const uint64_t* out_off, uint8_t* out, hipStream_t st) {
-    ReduceView R; R.rows = rows; R.ntargets = D.ntargets; R.partial = partial; R.target_chunk_begin = D.target_chunk_begin;
-    R.enc = enc; R.out_off = out_off; R.out = out; R.corr = nullptr;
+    ReduceView R = reduce_view(D, rows, partial, nullptr); R.enc = enc; R.out_off = out_off; R.out = out;
     ZKP_TRACED("k_sum_t<EdMsm>", st, launch_sum_ed(R, sums, st));
     ZKP_TRACED("k_encode", st, k_encode<<<dim3((rows + TW - 1) / TW, D.ntargets), TW, 0, st>>>(R, sums));
     return 0;
@@ -1081,8 +1068,8 @@ int prove_range_device_locked(uint64_t n, const uint64_t* d_value, const uint64_
     if ((rc = ensure_sub(sb, &dev().sub[0]))) return rc;
     HIP_TRY(hipEventRecord(sb.start, st));
     const uint32_t C = (uint32_t)n, M = 2 * C;
-    if ((rc = ensure_workspace(sb, M, C))) return rc;
-    Ws w; carve((uint8_t*)sb.ws, M, C, dev().max_chunks, &w);
+    Ws w{};
+    if ((rc = bind_workspace(sb, M, C, M, C, w))) return rc;
     w.V.n = 1u << lg; w.V.lg = lg;
     w.V.seeds = reinterpret_cast<const uint32_t*>(d_seeds); w.T.seeds = w.V.seeds;
     w.V.out = d_out;
@@ -1093,10 +1080,9 @@ int prove_range_device_locked(uint64_t n, const uint64_t* d_value, const uint64_
     HIP_TRY(hipEventRecord(sb.done, sb.stream)); sb.used = true;
     HIP_TRY(hipStreamWaitEvent(st, sb.done, 0));
     if (any_failed) {
-        Ws wf; carve((uint8_t*)sb.ws, sb.capM, sb.capC, dev().max_chunks, &wf);
-        HIP_TRY(hipMemsetAsync(wf.flag, 0, sizeof(int), st));
-        k_any_failed<<<(uint32_t)((n + TB - 1) / TB), TB, 0, st>>>(d_status, (uint32_t)n, wf.flag);
-        HIP_TRY(hipMemcpyAsync(any_failed, wf.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemsetAsync(w.flag, 0, sizeof(int), st));
+        k_any_failed<<<(uint32_t)((n + TB - 1) / TB), TB, 0, st>>>(d_status, (uint32_t)n, w.flag);
+        HIP_TRY(hipMemcpyAsync(any_failed, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
@@ -1111,9 +1097,9 @@ int run_jobs_on(SubBatch& sb, const HostJobs& H, const uint8_t* d_seeds, uint8_t
     int rc;
     if ((rc = ensure_family(lg)) || (rc = ensure_sub(sb))) return rc;
     if (sb.used) HIP_TRY(hipStreamWaitEvent(st, sb.done, 0));          // an asynchronous device-pointer call may still own this workspace
-    if ((rc = ensure_workspace(sb, M ? M : 1, C ? C : 1))) return rc;
-    Ws w; carve((uint8_t*)sb.ws, M ? M : 1, C ? C : 1, dev().max_chunks, &w);
-    w.V.M = M; w.T.C = C; w.V.n = 1u << lg; w.V.lg = lg;
+    Ws w{};
+    if ((rc = bind_workspace(sb, M ? M : 1, C ? C : 1, M, C, w))) return rc;      // the views carry the true counts, which may be 0
+    w.V.n = 1u << lg; w.V.lg = lg;
 #define UP(dst, vec) do { if (!(vec).empty()) HIP_TRY(hipMemcpyAsync((void*)(dst), (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, st)); } while (0)
     UP(w.J.v, H.v); UP(w.J.seed_ix, H.seed_ix); UP(w.J.proof_ix, H.proof_ix); UP(w.J.bl_plus, H.bl_plus); UP(w.J.bl_minus, H.bl_minus);
     UP(w.J.kind, H.kind); UP(w.J.proof_off, H.proof_off); UP(w.J.commit_off, H.commit_off);
