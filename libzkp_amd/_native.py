@@ -182,32 +182,26 @@ def lib():
         L.zkp_hip_batch_free.restype = None
         L.zkp_hip_profile_read_kernel.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
         L.zkp_hip_profile_read_kernel.restype = ctypes.c_int
-        if hasattr(L, "zkp_hip_bp_localise_counters"):      # (an older build loaded through ZKP_HIP_LIB has none; api.bp_verify_counters then raises)
-            L.zkp_hip_bp_localise_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
-            L.zkp_hip_bp_localise_counters.restype = ctypes.c_int
+        # the *_counters exports: a double, one uint64 per field, the reset flag (an older build loaded through ZKP_HIP_LIB lacks some; their api functions then raise)
+        for sym, n_fields in (("zkp_hip_bp_localise_counters", 3), ("zkp_hip_composites_counters", 3), ("zkp_stmt_counters", 4), ("libzkp_seal_counters", 4), ("zkpkeycheck_counters", 3)):
+            if hasattr(L, sym):
+                getattr(L, sym).argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * n_fields + [ctypes.c_int]
+                getattr(L, sym).restype = ctypes.c_int
         if hasattr(L, "zkp_hip_verify_composites"):         # (an older build loaded through ZKP_HIP_LIB has none; composite.verify_composite_proofs then raises)
             L.zkp_hip_verify_composites.argtypes = [u64, vp, vp, u32, vp]
             L.zkp_hip_verify_composites.restype = ctypes.c_int
-            L.zkp_hip_composites_counters.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
-            L.zkp_hip_composites_counters.restype = ctypes.c_int
         if hasattr(L, "zkp_stmt_verify"):                   # (an older build loaded through ZKP_HIP_LIB has none; api.verify_ops then raises)
             for f in (L.zkp_stmt_verify, L.zkp_stmt_verify_device):
                 f.argtypes = [u64, vp, vp, u64, vp, vp, vp, vp]
                 f.restype = ctypes.c_int
-            L.zkp_stmt_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
-            L.zkp_stmt_counters.restype = ctypes.c_int
         if hasattr(L, "libzkp_seal_composites"):            # (an older build loaded through ZKP_HIP_LIB has none; composite.create_composite_proofs then raises)
             L.libzkp_seal_composites.argtypes = [u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp]
             L.libzkp_seal_composites.restype = ctypes.c_int
             L.libzkp_seal_batch.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp, vp]
             L.libzkp_seal_batch.restype = ctypes.c_int
-            L.libzkp_seal_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 4 + [ctypes.c_int]
-            L.libzkp_seal_counters.restype = ctypes.c_int
         if hasattr(L, "zkpkeycheck_key"):                   # (an older build loaded through ZKP_HIP_LIB has none; api.check_key then raises)
             L.zkpkeycheck_key.argtypes = [ctypes.c_int, vp, u64, u32, ctypes.POINTER(KeyCheckReport)]
             L.zkpkeycheck_key.restype = ctypes.c_int
-            L.zkpkeycheck_counters.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(u64)] * 3 + [ctypes.c_int]
-            L.zkpkeycheck_counters.restype = ctypes.c_int
         # Release every device object while the interpreter and the HIP runtime are still fully alive (the library also
         # registers its own C atexit hook at the first initialisation; both are idempotent).  DESIGN.md "exit-time teardown".
         atexit.register(L.zkp_hip_shutdown)

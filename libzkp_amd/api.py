@@ -411,14 +411,22 @@ def check_key(kind, blob=None, twins=True, tables=None):
             "message": rep.message.decode("utf-8", "replace")}
 
 
+def _read_counters(symbol, lead, keys, reset):
+    """One family of the library's host-side counters through its export `symbol`: the leading arguments `lead` (the id, for the families of
+    zkp_hip_profile_read_kernel), then a double and one uint64 per key as outs, `reset` last.  {key: count, ..., "ms": host milliseconds}."""
+    ms, counts = ctypes.c_double(), [ctypes.c_uint64() for _ in keys]
+    _native.check(getattr(_native.lib(), symbol)(*lead, ctypes.byref(ms), *[ctypes.byref(c) for c in counts], 1 if reset else 0), symbol)
+    out = {k: int(c.value) for k, c in zip(keys, counts)}
+    out["ms"] = float(ms.value)
+    return out
+
+
 def key_check_counters(reset=True):
     """What the key loader's checks and check_key did, summed over the shards since the last reset (zkpkeycheck_counters,
     include/libzkp_hip_keycheck.h; always counted): {"loads_checked": key loads whose freshly built tables were self-checked,
     "entries_checked": table entries checked, "refused": keys refused at load or judged unsound by check_key, "ms": host time of the table
     checks}.  reset=True zeroes the counters."""
-    ms, a, b, c = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkpkeycheck_counters(ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), 1 if reset else 0), "zkpkeycheck_counters")
-    return {"loads_checked": int(a.value), "entries_checked": int(b.value), "refused": int(c.value), "ms": float(ms.value)}
+    return _read_counters("zkpkeycheck_counters", (), ("loads_checked", "entries_checked", "refused"), reset)
 
 
 def snark_commit_value_batch(values):
@@ -580,10 +588,7 @@ def groth16_verify_counters(reset=True):
     reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_G16_VERIFY; always counted): {"launches": segment checks run by localisation
     passes, "point_adds": envelopes given the per-envelope check after a failed batch check (the suspects, or the whole batch), "ms": host
     wall time from the failed checks' verdicts to the calls' returns}.  reset=True zeroes the counters."""
-    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_G16_VERIFY, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
-                  "zkp_hip_profile_read_kernel")
-    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+    return _read_counters("zkp_hip_profile_read_kernel", (_native.COUNTER_G16_VERIFY,), ("launches", "point_adds"), reset)
 
 
 def bp_verify_counters(reset=True):
@@ -592,10 +597,7 @@ def bp_verify_counters(reset=True):
     counted): {"failed_checks": batch checks (calls or slices) that did not stand, "segment_checks": segments checked by localisation
     passes, "jobs_again": jobs given the per-job pass after a failed check (the suspects, or the whole batch), "ms": host wall time from the
     failed checks' verdicts to the calls' returns}.  reset=True zeroes the counters."""
-    ms, failed, segments, jobs = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_bp_localise_counters(ctypes.byref(ms), ctypes.byref(failed), ctypes.byref(segments), ctypes.byref(jobs), 1 if reset else 0),
-                  "zkp_hip_bp_localise_counters")
-    return {"failed_checks": int(failed.value), "segment_checks": int(segments.value), "jobs_again": int(jobs.value), "ms": float(ms.value)}
+    return _read_counters("zkp_hip_bp_localise_counters", (), ("failed_checks", "segment_checks", "jobs_again"), reset)
 
 
 def batch_self_check_counters(reset=True):
@@ -603,10 +605,7 @@ def batch_self_check_counters(reset=True):
     shards since the last reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_BATCH_SELF_CHECK; always counted): {"launches": ops whose
     envelope went through its verifier, "point_adds": ops the self-check refused, "ms": host wall time from the end of proving to the end of
     verification}.  reset=True zeroes the counters."""
-    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_BATCH_SELF_CHECK, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
-                  "zkp_hip_profile_read_kernel")
-    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+    return _read_counters("zkp_hip_profile_read_kernel", (_native.COUNTER_BATCH_SELF_CHECK,), ("launches", "point_adds"), reset)
 
 
 def verify_fanout_counters(reset=True):
@@ -615,10 +614,7 @@ def verify_fanout_counters(reset=True):
     "point_adds": envelopes in those slices, "ms": host wall time of the fanned-out calls}.  A call that stayed on one shard -- one shard
     registered, ZKP_HIP_VERIFY_SHARDS=0, a thread that selected a shard, less than two minimum slices of work -- counts nothing.
     reset=True zeroes the counters."""
-    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_VERIFY_FANOUT, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
-                  "zkp_hip_profile_read_kernel")
-    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+    return _read_counters("zkp_hip_profile_read_kernel", (_native.COUNTER_VERIFY_FANOUT,), ("launches", "point_adds"), reset)
 
 
 def verify_mixed_counters(reset=True):
@@ -626,10 +622,7 @@ def verify_mixed_counters(reset=True):
     since the last reset (zkp_hip_profile_read_kernel id ZKP_HIP_COUNTER_VERIFY_MIXED; always counted): {"launches": scheme passes run,
     "point_adds": envelopes that got a row (everything the classification did not reject), "ms": host wall time of the calls}.
     reset=True zeroes the counters."""
-    ms, launches, adds = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_profile_read_kernel(_native.COUNTER_VERIFY_MIXED, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(adds), 1 if reset else 0),
-                  "zkp_hip_profile_read_kernel")
-    return {"launches": int(launches.value), "point_adds": int(adds.value), "ms": float(ms.value)}
+    return _read_counters("zkp_hip_profile_read_kernel", (_native.COUNTER_VERIFY_MIXED,), ("launches", "point_adds"), reset)
 
 
 def verify_envelopes(envelopes, expect=None):
@@ -720,9 +713,7 @@ def verify_statements_counters(reset=True):
     """What verify_ops did, summed over the shards since the last reset (zkp_stmt_counters, include/libzkp_hip_statements.h; always counted):
     {"envelopes": envelopes seen, "refused_envelope" / "refused_statement" / "refused_proof": envelopes refused by the envelope step, the
     statement step, their scheme's verifier, "ms": host wall time of the calls (of their slices)}.  reset=True zeroes the counters."""
-    ms, c = ctypes.c_double(), [ctypes.c_uint64() for _ in range(4)]
-    _native.check(_native.lib().zkp_stmt_counters(ctypes.byref(ms), *[ctypes.byref(x) for x in c], 1 if reset else 0), "zkp_stmt_counters")
-    return {"envelopes": int(c[0].value), "refused_envelope": int(c[1].value), "refused_statement": int(c[2].value), "refused_proof": int(c[3].value), "ms": float(ms.value)}
+    return _read_counters("zkp_stmt_counters", (), ("envelopes", "refused_envelope", "refused_statement", "refused_proof"), reset)
 
 
 def verify_equality_with_commitment_batch(proofs, commitments):
@@ -1056,9 +1047,7 @@ def seal_counters(reset=True):
     """What create_composite_proofs and process_ops_sealed did, summed over the shards since the last reset (libzkp_seal_counters,
     include/libzkp_hip_seal.h; always counted): {"containers": containers seen, "sealed": containers written, "envelopes": their inner
     proofs, "bytes": their bytes, "ms": host wall time of the device half of the calls}.  reset=True zeroes the counters."""
-    ms, a, b, c, d = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().libzkp_seal_counters(ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d), 1 if reset else 0), "libzkp_seal_counters")
-    return {"containers": int(a.value), "sealed": int(b.value), "envelopes": int(c.value), "bytes": int(d.value), "ms": float(ms.value)}
+    return _read_counters("libzkp_seal_counters", (), ("containers", "sealed", "envelopes", "bytes"), reset)
 
 
 KINDS = ("range", "threshold", "consistency", "equality", "membership", "improvement")

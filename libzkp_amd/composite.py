@@ -290,12 +290,8 @@ def verify_composites_counters(reset=True):
     include/libzkp_hip_composites.h; always counted): {"composites": containers seen, "malformed": containers that
     CompositeProof::from_bytes refuses, "envelopes": inner envelopes handed to the mixed verifier, "ms": host wall time of the calls}.
     reset=True zeroes the counters."""
-    import ctypes
-    from . import _native
-    ms, composites, malformed, envelopes = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    _native.check(_native.lib().zkp_hip_composites_counters(ctypes.byref(ms), ctypes.byref(composites), ctypes.byref(malformed), ctypes.byref(envelopes), 1 if reset else 0),
-                  "zkp_hip_composites_counters")
-    return {"composites": int(composites.value), "malformed": int(malformed.value), "envelopes": int(envelopes.value), "ms": float(ms.value)}
+    from . import api
+    return api._read_counters("zkp_hip_composites_counters", (), ("composites", "malformed", "envelopes"), reset)
 
 
 def verify_proofs_parallel(proofs):

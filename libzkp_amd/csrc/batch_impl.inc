@@ -377,7 +377,7 @@ int launch_shard(ShardPlan& P) {
 // other on the shard's stream, over that variant's arena rows against the staged parameters; the Groth16 binding; then the pack kernels with
 // the verdicts applied between the lengths and their prefix sum.  The host reads what the verifier cores read, and eight bytes of counters.
 int self_check_shard(ShardPlan& P) {
-    const auto t0 = std::chrono::steady_clock::now();
+    Tally tally(dev().counters, FAM_BATCH_SELF_CHECK, Tally::COMMITTED);          // a self-check that fails is not counted
     const uint32_t n = P.n;
     hipStream_t st = dev().stream;
     uint8_t *in = P.d_in, *ar = P.d_arena;
@@ -420,9 +420,8 @@ int self_check_shard(ShardPlan& P) {
     uint32_t cnt[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    Device::HostCounter& C = dev().counter(ZKP_HIP_COUNTER_BATCH_SELF_CHECK);
-    C.a += cnt[0]; C.b += cnt[1];
-    C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    tally[CTR_SELF_CHECK_VERIFIED] = cnt[0]; tally[CTR_SELF_CHECK_REFUSED] = cnt[1];
+    tally.commit();
     return 0;
 }
 int wait_shard(ShardPlan& P) {

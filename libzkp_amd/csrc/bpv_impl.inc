@@ -31,25 +31,12 @@ int fixed_base_sum(const DevLayout& D, uint32_t rows, const uint32_t* digits, ui
     return 0;
 }
 
-// What a call did after a batch check that did not stand (zkp_hip_bp_localise_counters): added to the shard's counters when the call
-// returns, whichever way
-struct BpLocaliseTally {
-    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    uint64_t segment_checks = 0, jobs_again = 0;
-    explicit BpLocaliseTally(Device& dv) : d(dv) {}
-    ~BpLocaliseTally() {
-        Device::BpLocaliseCounter& C = d.bp_localise;
-        C.failed_checks++; C.segment_checks += segment_checks; C.jobs_again += jobs_again;
-        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
 // After a batch check of V's M jobs (n envelopes) that did not stand (W: the weighted view, Q: the check's point terms): one check per
 // segment says where the bad jobs can be (bp_localise.h), only the suspect segments' jobs get the per-job pass, on compact arrays, and their
 // encodings land in enc among zeros.  *done = false: nothing was decided here and the caller verifies the whole batch (localisation
 // switched off, suspects in half of the batch, or -- against all odds -- no suspect at all).  job_base: the host's copy, or null.
 int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& Q, uint32_t n, uint32_t jobs_per, const uint32_t* job_base, uint32_t* enc,
-                BpLocaliseTally& tally, bool* done) {
+                Tally& tally, bool* done) {
     *done = false;
     if (env_int("ZKP_HIP_BP_LOCALISE", 1) == 0) return 0;
     int rc;
@@ -71,7 +58,7 @@ int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& 
     std::vector<uint8_t> suspect(count);
     HIP_TRY(hipMemcpyAsync(suspect.data(), lb + Ps.suspect, count, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    tally.segment_checks += count;
+    tally[CTR_BP_SEGMENT_CHECKS] += count;
     std::vector<uint32_t> offs((size_t)count + 1);
     const uint32_t Mc = bp_loc_offsets(g, n, jobs_per, job_base, suspect.data(), offs.data());
     if (Mc == 0 || bp_loc_whole_batch(Mc, M)) return 0;
@@ -91,7 +78,7 @@ int localise_bp(VfyState& S, const VfyView& V, const VfyView& W, const RlcView& 
     HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * M, st));
     bpv_launch_scatter(L, (const uint32_t*)(lb + Pc.J.enc), Mc, enc, M, st);
     HIP_TRY(hipGetLastError());
-    tally.jobs_again += Mc;
+    tally[CTR_BP_JOBS_AGAIN] += Mc;
     *done = true;
     return 0;
 }
@@ -137,7 +124,7 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
     else bpv_launch_parse_consistency(V, (uint32_t)n, stride, d_lens, st);
     uint32_t* enc = (uint32_t*)(base + P.J.enc);
     bool accepted_as_a_batch = false, located = false;      // located: the check did not stand and localise_bp has put the suspects' encodings into enc
-    std::unique_ptr<BpLocaliseTally> tally;                  // set once the batch check has not stood
+    std::unique_ptr<Tally> tally;                            // zkp_hip_bp_localise_counters: made once the batch check has not stood, added when the call returns, whichever way
     if (M) bpv_launch_decode(V, st);
     if (M && batch_mode) {
         // One check for the whole batch: sum_j rho_j (job j's combination) == 0 with fresh 128-bit weights from the OS, as
@@ -174,10 +161,10 @@ int verify_bp_device(int scheme, uint64_t n, const uint8_t* d_proofs, uint64_t s
             return fail(ZKP_HIP_E_RUNTIME, "Bulletproofs verification: the batch check did not stand and ZKP_HIP_BP_BATCH_VERIFY_ONLY is set");
         if (accepted_as_a_batch) HIP_TRY(hipMemsetAsync(enc, 0, (size_t)32 * Mw, st));                // every surviving job's sum is the identity
         else {
-            tally.reset(new BpLocaliseTally(dev()));
+            tally = bp_localise_tally(dev().counters);
             if ((rc = localise_bp(S, V, W, Q, (uint32_t)n, jobs_per, consistency ? job_base.data() : nullptr, enc, *tally, &located))) return rc;
             if (!located) {
-                tally->jobs_again += M;
+                (*tally)[CTR_BP_JOBS_AGAIN] += M;
                 HIP_TRY(hipMemsetAsync(base + P.J.zero0, 0, P.J.zero1 - P.J.zero0, st));          // weighted scalars out, per-job path below
             }
         }
@@ -251,22 +238,9 @@ int zkp_hip_verify_consistency_batch(uint64_t n, const uint8_t* proofs, uint64_t
     return rc ? rc : verify_bp_call(ZKP_HIP_OP_CONSISTENCY, n, proofs, stride, lens, nullptr, nullptr, ok);
 } ZKP_API_CATCH_INT
 
-// accumulated over all shards (BpLocaliseTally); needs no device
+// accumulated over all shards; needs no device
 int zkp_hip_bp_localise_counters(double* ms, uint64_t* failed_checks, uint64_t* segment_checks, uint64_t* jobs_again, int reset) try {
-    std::vector<Device*> shards;
-    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
-    Device::BpLocaliseCounter T;
-    for (Device* d : shards) {
-        std::lock_guard<std::mutex> dl(d->mu);
-        Device::BpLocaliseCounter& C = d->bp_localise;
-        T.ms += C.ms; T.failed_checks += C.failed_checks; T.segment_checks += C.segment_checks; T.jobs_again += C.jobs_again;
-        if (reset) C = Device::BpLocaliseCounter();
-    }
-    if (ms) *ms = T.ms;
-    if (failed_checks) *failed_checks = T.failed_checks;
-    if (segment_checks) *segment_checks = T.segment_checks;
-    if (jobs_again) *jobs_again = T.jobs_again;
-    return 0;
+    return read_counters(FAM_BP_LOCALISE, ms, {failed_checks, segment_checks, jobs_again}, reset);
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

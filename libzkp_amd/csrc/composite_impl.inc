@@ -32,23 +32,11 @@ struct CompCall {
     uint64_t envelopes = 0;
 };
 
-// added to the bound shard's counters when a slice returns, whichever way
-struct CompTally {
-    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    uint64_t composites = 0, malformed = 0, envelopes = 0;
-    explicit CompTally(Device& dv) : d(dv) {}
-    ~CompTally() {
-        Device::CompositesCounter& C = d.composites;
-        C.composites += composites; C.malformed += malformed; C.envelopes += envelopes;
-        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
 // The containers [lo, lo + m) of the call on the bound shard: digests first, then the inner envelopes of the containers that stand through
 // the mixed verifier's core, then the fold.
 int composites_slice(const CompCall& K, uint64_t lo, uint64_t m) {
-    CompTally tally(dev());
-    tally.composites = m;
+    Tally tally(dev().counters, FAM_COMPOSITES);          // added when the slice returns, whichever way
+    tally[CTR_COMP_COMPOSITES] = m;
     hipStream_t st = dev().stream;
     uint8_t* status = K.status + lo;
     std::vector<uint32_t> good; good.reserve(m);          // slice indices of the well-formed containers
@@ -59,7 +47,7 @@ int composites_slice(const CompCall& K, uint64_t lo, uint64_t m) {
         good.push_back((uint32_t)i);
         span_lo = std::min(span_lo, K.off[lo + i]); span_hi = std::max(span_hi, K.off[lo + i + 1]);
     }
-    tally.malformed = m - good.size();
+    tally[CTR_COMP_MALFORMED] = m - good.size();
     if (good.empty()) return 0;
     // lanes: longest stream first
     std::vector<uint32_t> by_len(good);
@@ -101,7 +89,7 @@ int composites_slice(const CompCall& K, uint64_t lo, uint64_t m) {
         status[by_len[j]] = CP_ACCEPTED; standing++;
         envelopes += K.walk[lo + by_len[j]].nproofs; packed_bytes += K.walk[lo + by_len[j]].proof_bytes;
     }
-    tally.malformed = m - standing;
+    tally[CTR_COMP_MALFORMED] = m - standing;
     if ((K.flags & ZKP_HIP_COMPOSITES_INTEGRITY_ONLY) || envelopes == 0) return 0;
     // the inner envelopes of the containers that stand, in container order: where each lies, where it goes
     std::vector<uint64_t> src(envelopes), poff(envelopes + 1), env0(m + 1);
@@ -109,15 +97,10 @@ int composites_slice(const CompCall& K, uint64_t lo, uint64_t m) {
     for (uint64_t i = 0; i < m; i++) {
         env0[i] = e;
         if (status[i] != CP_ACCEPTED) continue;
-        uint64_t at = K.off[lo + i] + 12;
-        for (uint32_t k = 0; k < K.walk[lo + i].nproofs; k++) {
-            const uint64_t len = ve_le(K.blob + at, 4);
-            src[e] = at + 4 - span_lo; poff[e] = at_packed; e++;
-            at += 4 + len; at_packed += len;
-        }
+        comp_each_envelope(K.blob, K.off[lo + i], K.walk[lo + i].nproofs, [&](uint64_t at, uint64_t len) { src[e] = at - span_lo; poff[e] = at_packed; e++; at_packed += len; });
     }
     env0[m] = e; poff[e] = at_packed;
-    tally.envelopes = envelopes;
+    tally[CTR_COMP_ENVELOPES] = envelopes;
     uint8_t *d_packed = nullptr, *d_ok = nullptr, *d_status = nullptr; uint64_t *d_src = nullptr, *d_poff = nullptr, *d_env0 = nullptr;
     HIP_TRY(mem.alloc(&d_packed, packed_bytes)); HIP_TRY(mem.alloc(&d_ok, envelopes)); HIP_TRY(mem.alloc(&d_status, m));
     HIP_TRY(mem.alloc(&d_src, 8 * envelopes)); HIP_TRY(mem.alloc(&d_poff, 8 * (envelopes + 1))); HIP_TRY(mem.alloc(&d_env0, 8 * (m + 1)));
@@ -136,34 +119,23 @@ int composites_slice(const CompCall& K, uint64_t lo, uint64_t m) {
     return 0;
 }
 
-// The fan-out data (verify_call).  A container weighs what its envelopes weigh (ve_weight), at least 1; the minimum slice is the larger of
-// the two batch-check thresholds in force; shards that lack a usable key of a Groth16 circuit whose scheme byte occurs in a well-formed
-// container take no part.
+// The fan-out data (verify_call) through list_fanout (venv_impl.inc).  A container weighs what its envelopes weigh (ve_scheme_weight), at least 1;
+// a key is needed when its scheme byte occurs in a well-formed container.
 int composites_plan(const CompCall& K, const std::vector<Device*>& shards, VerifyFanout& F) {
     std::vector<uint32_t> weights(K.n, 1);
     bool need[2] = {false, false};
     if (!(K.flags & ZKP_HIP_COMPOSITES_INTEGRITY_ONLY)) for (uint64_t i = 0; i < K.n; i++) {
         if (!K.walk[i].ok) continue;
-        uint64_t at = K.off[i] + 12, w = 0;
-        for (uint32_t k = 0; k < K.walk[i].nproofs; k++) {
-            const uint64_t len = ve_le(K.blob + at, 4);
-            const uint8_t s = K.blob[at + 5];
-            w += s == 1 ? 2u : s == 6 ? ve_consistency_jobs(K.blob + at + 4, len) : 1u;
+        uint64_t w = 0;
+        comp_each_envelope(K.blob, K.off[i], K.walk[i].nproofs, [&](uint64_t at, uint64_t len) {
+            const uint8_t s = K.blob[at + 1];
+            w += ve_scheme_weight(s, K.blob + at, len);
             if (s == ZKP_HIP_OP_EQUALITY) need[G16_EQUALITY] = true;
             if (s == ZKP_HIP_OP_MEMBERSHIP) need[G16_MEMBERSHIP] = true;
-            at += 4 + len;
-        }
+        });
         weights[i] = (uint32_t)std::min<uint64_t>(w, 0xffffffffu);
     }
-    F.prefix.resize(K.n + 1);
-    vs_prefix(K.n, weights.data(), F.prefix.data());
-    for (Device* d : shards) {
-        bool has = true;
-        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has = has && g16_shard_holds_vk(d, kind);
-        F.holds.push_back(has);
-    }
-    F.unit = 0; F.min_jobs = std::max(bp_min_slice(), g16_min_slice());
-    return 0;
+    return list_fanout(weights, need, shards, F);
 }
 
 }  // namespace
@@ -175,7 +147,7 @@ int zkp_hip_verify_composites(uint64_t n, const uint8_t* blob, const uint64_t* o
     int rc = check_batch_size(n);
     if (rc) return rc;
     if (!off || !status) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    if (!blob && off[n] > off[0]) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    if (null_blob_of_span(blob, off, n)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     if (flags & ~ZKP_HIP_COMPOSITES_INTEGRITY_ONLY) return fail(ZKP_HIP_E_ARGUMENT, "unknown flag");
     CompCall K{n, blob, off, flags, status, {}, {}};
     K.walk.reserve(n);
@@ -189,20 +161,7 @@ int zkp_hip_verify_composites(uint64_t n, const uint8_t* blob, const uint64_t* o
 } ZKP_API_CATCH_INT
 
 int zkp_hip_composites_counters(double* ms, uint64_t* composites, uint64_t* malformed, uint64_t* envelopes, int reset) try {
-    std::vector<Device*> shards;
-    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
-    Device::CompositesCounter T;
-    for (Device* d : shards) {
-        std::lock_guard<std::mutex> dl(d->mu);
-        Device::CompositesCounter& C = d->composites;
-        T.ms += C.ms; T.composites += C.composites; T.malformed += C.malformed; T.envelopes += C.envelopes;
-        if (reset) C = Device::CompositesCounter();
-    }
-    if (ms) *ms = T.ms;
-    if (composites) *composites = T.composites;
-    if (malformed) *malformed = T.malformed;
-    if (envelopes) *envelopes = T.envelopes;
-    return 0;
+    return read_counters(FAM_COMPOSITES, ms, {composites, malformed, envelopes}, reset);
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

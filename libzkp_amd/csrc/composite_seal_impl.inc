@@ -21,18 +21,6 @@ __global__ void __launch_bounds__(64) k_comp_seal(uint8_t* out, uint64_t bytes, 
 
 namespace {
 
-// added to the bound shard's counters when a call returns, whichever way
-struct SealTally {
-    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    uint64_t containers = 0, sealed = 0, envelopes = 0, bytes = 0;
-    explicit SealTally(Device& dv) : d(dv) {}
-    ~SealTally() {
-        Device::SealCounter& C = d.seal;
-        C.containers += containers; C.sealed += sealed; C.envelopes += envelopes; C.bytes += bytes;
-        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
 // The arguments both forms share, checked before anything is sized from them
 int seal_check_args(uint64_t n, uint64_t n_env, const uint64_t* first, const uint8_t* meta_blob, const uint64_t* meta_off, const uint8_t* out, uint64_t out_cap,
                     const uint64_t* out_off, const uint8_t* status) {
@@ -42,7 +30,7 @@ int seal_check_args(uint64_t n, uint64_t n_env, const uint64_t* first, const uin
     for (uint64_t i = 0; i < n; i++) if (first[i] > first[i + 1]) return fail(ZKP_HIP_E_ARGUMENT, "first[] must not decrease");
     if (meta_off) {
         for (uint64_t i = 0; i < n; i++) if (meta_off[i] > meta_off[i + 1]) return fail(ZKP_HIP_E_ARGUMENT, "meta_off[] must not decrease");
-        if (!meta_blob && meta_off[n] > meta_off[0]) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+        if (null_blob_of_span(meta_blob, meta_off, n)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     }
     return 0;
 }
@@ -59,8 +47,8 @@ int seal_publish(const SealPlan& P, uint64_t n, uint64_t out_cap, uint64_t* out_
 // on the device, or null: h_env[env_lo .. env_hi) is uploaded.  Returns 0, or 1 when some container was not sealed.
 int seal_run(const SealPlan& P, uint64_t n, const uint64_t* env_off, const uint8_t* h_env, const uint8_t* d_env, uint64_t env_lo, uint64_t env_hi,
              const uint8_t* meta_blob, const uint64_t* meta_off, uint8_t* out) {
-    SealTally tally(dev());
-    tally.containers = n; tally.sealed = P.rec.size(); tally.envelopes = P.envelopes; tally.bytes = P.out_off[n];
+    Tally tally(dev().counters, FAM_SEAL);          // added when the call returns, whichever way
+    tally[CTR_SEAL_CONTAINERS] = n; tally[CTR_SEAL_SEALED] = P.rec.size(); tally[CTR_SEAL_ENVELOPES] = P.envelopes; tally[CTR_SEAL_BYTES] = P.out_off[n];
     const int any = P.rec.size() != n ? 1 : 0;
     if (P.rec.empty()) return any;
     hipStream_t st = dev().stream;
@@ -121,7 +109,7 @@ int libzkp_seal_composites(uint64_t n, const uint8_t* env_blob, const uint64_t* 
     if (n == 0) return 0;
     int rc = seal_check_args(n, n_env, first, meta_blob, meta_off, out, out_cap, out_off, status);
     if (rc) return rc;
-    if (n_env && (!env_off || (!env_blob && env_off[n_env] > env_off[0]))) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    if (n_env && (!env_off || null_blob_of_span(env_blob, env_off, n_env))) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     return seal_host(n, env_blob, env_off, n_env, nullptr, first, meta_blob, meta_off, out, out_cap, out_off, status);
 } ZKP_API_CATCH_INT
 
@@ -155,21 +143,7 @@ int libzkp_seal_batch(zkp_hip_batch* batch, uint64_t n, const uint64_t* first_op
 } ZKP_API_CATCH_INT
 
 int libzkp_seal_counters(double* ms, uint64_t* containers, uint64_t* sealed, uint64_t* envelopes, uint64_t* bytes, int reset) try {
-    std::vector<Device*> shards;
-    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
-    Device::SealCounter T;
-    for (Device* d : shards) {
-        std::lock_guard<std::mutex> dl(d->mu);
-        Device::SealCounter& C = d->seal;
-        T.ms += C.ms; T.containers += C.containers; T.sealed += C.sealed; T.envelopes += C.envelopes; T.bytes += C.bytes;
-        if (reset) C = Device::SealCounter();
-    }
-    if (ms) *ms = T.ms;
-    if (containers) *containers = T.containers;
-    if (sealed) *sealed = T.sealed;
-    if (envelopes) *envelopes = T.envelopes;
-    if (bytes) *bytes = T.bytes;
-    return 0;
+    return read_counters(FAM_SEAL, ms, {containers, sealed, envelopes, bytes}, reset);
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

@@ -132,6 +132,16 @@ inline CompWalk comp_walk(const uint8_t* blob, uint64_t lo, uint64_t hi, uint64_
     W.hashed = (uint32_t)(CP_PREFIX_BYTES + proof_bytes + meta_bytes);          // (< 4 MiB + 20: every hashed byte lies in the container, once)
     return W;
 }
+// The inner envelopes of a container that comp_walk found well-formed (its first byte at blob[lo], W.nproofs of them), in order: f(at, len)
+// for the envelope of `len` bytes at blob[at], behind its length prefix.  One copy for the fan-out weights and the pack lists (composite_impl.inc).
+template <class F> inline void comp_each_envelope(const uint8_t* blob, uint64_t lo, uint32_t nproofs, F f) {
+    uint64_t at = lo + 12;
+    for (uint32_t k = 0; k < nproofs; k++) {
+        const uint64_t len = ve_le(blob + at, 4);
+        f(at + 4, len);
+        at += 4 + len;
+    }
+}
 
 // What a digest lane reads of its container (40 bytes)
 struct CompLane {

@@ -238,7 +238,7 @@ static const char* const KC_TABLE_NAME[3] = {"G1", "G2", "VK"};
 struct KcTableResult { uint64_t entries = 0; uint32_t bad_pairs = 0, bad_entries = 0, slot = 0, win = 0, ent = 0; std::vector<uint32_t> pair_bad; };
 // every entry of the `nslots` slots of `table` against d_bases; waits for the result.  Counts into the shard's keycheck counters.
 int kc_check_table(bool g2, const uint32_t* d_bases, uint32_t nslots, const uint32_t* table, bool msm_form, const G16Radix& rx, KcTableResult& R, bool want_pairs = false) {
-    const auto t0 = std::chrono::steady_clock::now();
+    Tally tally(dev().counters, FAM_KEY_CHECK, Tally::COMMITTED);          // a check that fails to run is not counted
     R = KcTableResult();
     if (nslots == 0) return 0;
     DevScope mem;
@@ -252,8 +252,8 @@ int kc_check_table(bool g2, const uint32_t* d_bases, uint32_t nslots, const uint
     HIP_TRY(hipStreamSynchronize(dev().stream));
     R.entries = (uint64_t)nslots * rx.slot_ent; R.bad_pairs = out[0]; R.bad_entries = out[1];
     if (R.bad_pairs) { const uint64_t key = (uint64_t)out[3] << 32 | out[2]; R.slot = (uint32_t)(key >> 40); R.win = (uint32_t)(key >> 32) & 0xffu; R.ent = (uint32_t)key; }
-    Device::KeyCheckCounter& C = dev().keycheck;
-    C.entries_checked += R.entries; C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    tally[CTR_KEY_ENTRIES_CHECKED] = R.entries;
+    tally.commit();
     return 0;
 }
 // a freshly built table: the flip diagnostic when it names this table, then the self-check.  `which`: 0 G1, 1 G2, 2 VK (KC_TABLE_NAME)
@@ -269,7 +269,7 @@ int kc_after_build(int which, const uint32_t* d_bases, uint32_t nslots, uint32_t
     KcTableResult R; int rc;
     if ((rc = kc_check_table(g2, d_bases, nslots, table, msm_form, rx, R))) return rc;
     if (!R.bad_pairs) return 0;
-    dev().keycheck.refused++;
+    dev().counters[FAM_KEY_CHECK].v[CTR_KEY_REFUSED]++;
     char msg[200];
     snprintf(msg, sizeof msg, "Groth16 key tables failed their self-check (%s slot %u window %u, %u inconsistent windows)", KC_TABLE_NAME[which], R.slot, R.win, R.bad_pairs);
     return fail(ZKP_HIP_E_RUNTIME, msg);
@@ -296,7 +296,7 @@ int kc_load_subgroup(const G16VkBlob& B, const G16PkBlob* Q) {
     if ((rc = kc_subgroup_run(L, ok))) return rc;
     for (size_t i = 0; i < ok.size(); i++) {
         if (ok[i]) continue;
-        dev().keycheck.refused++;
+        dev().counters[FAM_KEY_CHECK].v[CTR_KEY_REFUSED]++;
         char name[48], msg[160]; g16_g2_point_name(name, sizeof name, L.index[i]);
         snprintf(msg, sizeof msg, "key point %s is not in the prime-order subgroup of G2", name);
         return fail(ZKP_HIP_E_ARGUMENT, msg);
@@ -352,11 +352,12 @@ int load_key_locked(int kind, const uint8_t* pk, uint64_t len) {
     G16Key& K = g16s().key[kind];
     if (K.loaded || K.shared_tables >= 0 || !K.allocs.empty()) release_key(K);
     int rc;
-    const uint64_t checked_before = dev().keycheck.entries_checked;
+    ShardCounter& kc = dev().counters[FAM_KEY_CHECK];
+    const uint64_t checked_before = kc.v[CTR_KEY_ENTRIES_CHECKED];
     try { rc = load_key_body(kind, pk, len); }
     catch (...) { release_key(K); throw; }               // (the ABI's barrier reports it; the registry reference and the blocks are not leaked)
     if (rc) { const std::string keep = t_err; release_key(K); t_err = keep; }      // a failed load leaves no table reference and no allocation behind
-    if (dev().keycheck.entries_checked != checked_before) dev().keycheck.loads_checked++;      // freshly built tables went through the self-check
+    if (kc.v[CTR_KEY_ENTRIES_CHECKED] != checked_before) kc.v[CTR_KEY_LOADS_CHECKED]++;      // freshly built tables went through the self-check
     return rc;
 }
 // The verifying-key part of a key, shared by both formats: gamma, delta, gamma_abc_g1 and the constant Miller-loop factor of
@@ -546,7 +547,7 @@ int keycheck_locked(int kind, const uint8_t* key, uint64_t len, uint32_t what, z
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     memset(&rep, 0, sizeof rep);
     rep.format = ZKP_KEYCHECK_FORMAT_UNKNOWN; rep.g2_first_outside = -1; rep.twins_query_ok = rep.twins_beta_delta_ok = -1; rep.table_first_which = -1;
-    auto verdict = [&](uint32_t v, const char* msg) { rep.verdict = v; snprintf(rep.message, sizeof rep.message, "%s", msg); dev().keycheck.refused++; return 0; };
+    auto verdict = [&](uint32_t v, const char* msg) { rep.verdict = v; snprintf(rep.message, sizeof rep.message, "%s", msg); dev().counters[FAM_KEY_CHECK].v[CTR_KEY_REFUSED]++; return 0; };
     const HostR1CS cs = kind == G16_EQUALITY ? build_equality_r1cs() : build_membership_r1cs();
     int rc;
     // POINTS
@@ -870,24 +871,11 @@ int verify_g16_device(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride,
     return 0;
 }
 
-// What a call did after a batch check that did not stand (ZKP_HIP_COUNTER_G16_VERIFY of zkp_hip_profile_read_kernel): added to the shard's
-// counters when the call returns, whichever way
-struct G16VerifyTally {
-    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    uint64_t segment_checks = 0, envelopes = 0;
-    explicit G16VerifyTally(Device& dv) : d(dv) {}
-    ~G16VerifyTally() {
-        Device::HostCounter& C = d.counter(ZKP_HIP_COUNTER_G16_VERIFY);
-        C.a += segment_checks; C.b += envelopes;
-        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
 // After a batch check of these n envelopes that did not stand (d_rlc: its scratch, d_ok / ok: its verdicts, on the device and on the host):
 // one check per segment says where the bad envelopes can be (g16_localise.h), and only the suspect segments' envelopes get the per-envelope
 // check.  *done = false: nothing was decided here and the caller verifies the whole batch (localisation switched off, or suspects in half of it).
 int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, const uint32_t* d_len, uint32_t n, uint8_t* d_rlc, uint8_t* d_ok, uint8_t* ok,
-                 const uint32_t counters[4], DevScope& mem, G16VerifyTally& tally, bool* done) {
+                 const uint32_t counters[4], DevScope& mem, Tally& tally, bool* done) {
     *done = false;
     if (env_int("ZKP_HIP_G16_LOCALISE", 1) == 0) return 0;
     hipStream_t st = dev().stream;
@@ -903,7 +891,7 @@ int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, cons
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(suspect.data(), d_loc, g.count, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    tally.segment_checks += g.count;
+    tally[CTR_G16_SEGMENT_CHECKS] += g.count;
     std::vector<uint32_t> off((size_t)g.count + 1);
     const uint32_t m = g16_loc_offsets(g, n, suspect.data(), off.data());
     if (g16_loc_whole_batch(m, n)) return 0;
@@ -915,7 +903,7 @@ int localise_g16(int kind, G16Key& K, const uint8_t* d_in, uint64_t stride, cons
     HIP_TRY(hipMemcpyAsync(d_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, st));
     g16_launch_compact(d_in, stride, d_len, n, g, d_loc, d_off, d_in2, d_len2, st);
     HIP_TRY(hipGetLastError());
-    tally.envelopes += m;
+    tally[CTR_G16_ENVELOPES] += m;
     int rc = verify_g16_device(kind, K, d_in2, stride, d_len2, m, d_ok2, nullptr, true, mem);
     if (rc) return rc;
     g16_launch_scatter(n, g, d_loc, d_off, d_ok2, d_ok, st);
@@ -938,7 +926,7 @@ int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, 
     if (!K.vk_ready) return fail(ZKP_HIP_E_ARGUMENT, "no (usable) key loaded for this circuit (zkp_hip_groth16_load_key)");
     hipStream_t st = dev().stream;
     static const int use_vm = env_int("ZKP_HIP_G16_VERIFY_VM", 1);
-    std::unique_ptr<G16VerifyTally> tally;          // set once a batch check has not stood
+    std::unique_ptr<Tally> tally;          // ZKP_HIP_COUNTER_G16_VERIFY: made once a batch check has not stood, added when the call returns, whichever way
     if (use_vm) {
         G16VmTables& T = g16s().vm;
         if (!T.ready) {
@@ -970,12 +958,12 @@ int verify_g16_core(int kind, uint64_t n, const uint8_t* d_in, uint64_t stride, 
                 char msg[160]; snprintf(msg, sizeof msg, "the batch check did not stand (special %u, outside the subgroup %u, anomalies %u, product is one: %u)", counters[0], counters[1], counters[2], counters[3]);
                 return fail(ZKP_HIP_E_RUNTIME, msg);
             }
-            tally.reset(new G16VerifyTally(dev()));
+            tally.reset(new Tally(dev().counters, FAM_G16_VERIFY));
             bool done = false;
             const int rc = localise_g16(kind, K, d_in, stride, d_len, (uint32_t)n, d_rlc, d_ok, ok, counters, mem, *tally, &done);
             if (rc) return rc;
             if (done) return 0;
-            tally->envelopes += n;
+            (*tally)[CTR_G16_ENVELOPES] += n;
         }
     }
     return verify_g16_device(kind, K, d_in, stride, d_len, (uint32_t)n, d_ok, ok, use_vm != 0, mem);
@@ -1066,20 +1054,7 @@ int zkpkeycheck_key(int kind, const uint8_t* key, uint64_t len, uint32_t what, z
 } ZKP_API_CATCH_INT
 
 int zkpkeycheck_counters(double* ms, uint64_t* loads_checked, uint64_t* entries_checked, uint64_t* refused, int reset) try {
-    std::vector<Device*> shards;
-    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
-    Device::KeyCheckCounter T;
-    for (Device* d : shards) {
-        std::lock_guard<std::mutex> dl(d->mu);
-        Device::KeyCheckCounter& C = d->keycheck;
-        T.ms += C.ms; T.loads_checked += C.loads_checked; T.entries_checked += C.entries_checked; T.refused += C.refused;
-        if (reset) C = Device::KeyCheckCounter();
-    }
-    if (ms) *ms = T.ms;
-    if (loads_checked) *loads_checked = T.loads_checked;
-    if (entries_checked) *entries_checked = T.entries_checked;
-    if (refused) *refused = T.refused;
-    return 0;
+    return read_counters(FAM_KEY_CHECK, ms, {loads_checked, entries_checked, refused}, reset);
 } ZKP_API_CATCH_INT
 
 int zkp_hip_groth16_generate_key(int kind, const uint8_t* setup_seed, uint8_t* pk_out, uint64_t pk_cap, uint64_t* pk_len,

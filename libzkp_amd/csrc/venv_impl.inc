@@ -107,7 +107,7 @@ int verify_records_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off
 // The call on device pointers, on the bound shard: classification, then verify_records_core with k_venv_apply; the verdicts into d_ok
 // (device, n bytes); ok_host (may be null) also receives them before the wait that ends the call.
 int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_off, const uint8_t* d_expect, uint8_t* d_ok, uint8_t* ok_host) {
-    const auto t0 = std::chrono::steady_clock::now();
+    Tally tally(dev().counters, FAM_VERIFY_MIXED, Tally::COMMITTED);          // a call that fails is not counted
     hipStream_t st = dev().stream;
     DevScope mem;
     VenvRecord* d_rec = nullptr;
@@ -123,33 +123,40 @@ int verify_envelopes_core(uint64_t n, const uint8_t* d_blob, const uint64_t* d_o
         return 0;
     });
     if (rc) return rc;
-    Device::HostCounter& C = dev().counter(ZKP_HIP_COUNTER_VERIFY_MIXED);
-    C.a += passes; C.b += live;
-    C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    tally[CTR_MIXED_PASSES] = passes; tally[CTR_MIXED_LIVE] = live;
+    tally.commit();
     return 0;
 }
 
-// The host-buffer form on the bound shard, for the m envelopes whose offsets start at `off` (m + 1 entries): one upload of the bytes they
-// span, their offsets re-based to that span, and `expect`; then the core.
+// The host-buffer form on the bound shard, for the m envelopes whose offsets start at `off` (m + 1 entries): the span's upload (SpanUpload)
+// and `expect`; then the core.
 int verify_envelopes_host(uint64_t m, const uint8_t* blob, const uint64_t* off, const uint8_t* expect, uint8_t* ok) {
-    if (off[m] < off[0]) { memset(ok, 0, m); return 0; }          // no envelope lies inside an empty span
-    const uint64_t first = off[0], bytes = off[m] - first;
-    // (an offset below `first` wraps to a value beyond `bytes`, so the classification rejects its envelope as outside the span)
-    std::vector<uint64_t> rel(m + 1);
-    for (uint64_t i = 0; i <= m; i++) rel[i] = off[i] - first;
-    hipStream_t st = dev().stream;
-    DevScope mem;
-    uint8_t *d_blob = nullptr, *d_expect = nullptr, *d_ok = nullptr; uint64_t* d_off = nullptr;
-    HIP_TRY(mem.alloc(&d_blob, bytes)); HIP_TRY(mem.alloc(&d_off, 8 * (m + 1))); HIP_TRY(mem.alloc(&d_ok, m));
-    if (expect) HIP_TRY(mem.alloc(&d_expect, m));
-    if (bytes) HIP_TRY(hipMemcpyAsync(d_blob, blob + first, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), 8 * (m + 1), hipMemcpyHostToDevice, st));
-    if (expect) HIP_TRY(hipMemcpyAsync(d_expect, expect, m, hipMemcpyHostToDevice, st));
-    return verify_envelopes_core(m, d_blob, d_off, d_expect, d_ok, ok);
+    SpanUpload up; bool empty;
+    int rc = up.open(m, blob, off, &empty);
+    if (rc) return rc;
+    if (empty) { memset(ok, 0, m); return 0; }
+    uint8_t* d_expect = nullptr;
+    if (expect) { HIP_TRY(up.mem.alloc(&d_expect, m)); HIP_TRY(hipMemcpyAsync(d_expect, expect, m, hipMemcpyHostToDevice, dev().stream)); }
+    return verify_envelopes_core(m, up.d_blob, up.d_off, d_expect, up.d_ok, ok);
 }
 
-// The fan-out data of the host-buffer form (verify_call).  Weights: ve_weight.  Minimum slice: the larger of the two batch-check thresholds
-// in force.  Shards that lack a usable key of a Groth16 circuit whose scheme byte occurs in the list take no part.
+// The fan-out data of a host-buffer call over a list of envelopes of any scheme (verify_call), for this file's call, vst_impl.inc's and
+// composite_impl.inc's: the rule is vs_list_fanout (verify_shards.h).  weights: one per item of the list; need[kind]: the list holds work for
+// the Groth16 circuit `kind`, so a shard takes part only with a usable key of it -- asked here, of every candidate, and nowhere else.
+// Minimum slice: the larger of the two batch-check thresholds in force.
+int list_fanout(const std::vector<uint32_t>& weights, const bool (&need)[2], const std::vector<Device*>& shards, VerifyFanout& F) {
+    static_assert(G16_EQUALITY == 0 && G16_MEMBERSHIP == 1, "need[] and the key table are indexed by circuit kind");
+    std::vector<uint8_t> has_key(2 * shards.size(), 0);
+    for (size_t s = 0; s < shards.size(); s++) {
+        bool has = true;          // (a shard that lacks the first needed key is not asked for the second: it takes no part either way)
+        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has_key[2 * s + kind] = has = has && g16_shard_holds_vk(shards[s], kind);
+    }
+    F.prefix.resize(weights.size() + 1); F.holds.resize(shards.size());
+    vs_list_fanout(weights.size(), weights.data(), need[G16_EQUALITY], need[G16_MEMBERSHIP], (uint32_t)shards.size(), has_key.data(), bp_min_slice(), g16_min_slice(),
+                   F.prefix.data(), F.holds.data(), &F.unit, &F.min_jobs);
+    return 0;
+}
+// The mixed verifier's: weights from ve_weight; a key is needed when its scheme byte occurs in an envelope that lies inside the blob.
 int verify_envelopes_plan(uint64_t n, const uint8_t* blob, const uint64_t* off, const std::vector<Device*>& shards, VerifyFanout& F) {
     std::vector<uint32_t> weights(n);
     bool need[2] = {false, false};
@@ -161,15 +168,7 @@ int verify_envelopes_plan(uint64_t n, const uint8_t* blob, const uint64_t* off, 
             if (s == ZKP_HIP_OP_MEMBERSHIP) need[G16_MEMBERSHIP] = true;
         }
     }
-    F.prefix.resize(n + 1);
-    vs_prefix(n, weights.data(), F.prefix.data());
-    for (Device* d : shards) {
-        bool has = true;
-        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has = has && g16_shard_holds_vk(d, kind);
-        F.holds.push_back(has);
-    }
-    F.unit = 0; F.min_jobs = std::max(bp_min_slice(), g16_min_slice());
-    return 0;
+    return list_fanout(weights, need, shards, F);
 }
 
 }  // namespace
@@ -181,7 +180,7 @@ int zkp_hip_verify_envelopes(uint64_t n, const uint8_t* blob, const uint64_t* of
     int rc = check_batch_size(n);
     if (rc) return rc;
     if (!off || !ok) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    if (!blob && off[n] > off[0]) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    if (null_blob_of_span(blob, off, n)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     return verify_call(n, [&](const std::vector<Device*>& shards, VerifyFanout& F) { return verify_envelopes_plan(n, blob, off, shards, F); },
                        [&](uint64_t lo, uint64_t m) { return verify_envelopes_host(m, blob, off + lo, expect ? expect + lo : nullptr, ok + lo); });
 } ZKP_API_CATCH_INT

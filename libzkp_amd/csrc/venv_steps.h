@@ -190,12 +190,14 @@ ZKP_HD inline uint8_t step_venv_apply(const VenvView& V, uint64_t i) {
 }
 
 // Weight of an envelope in the plan that cuts a host call over the registered shards (verify_shards.h), from a host peek at its scheme byte:
-// a range envelope 2 jobs, a consistency envelope its k - 1, everything else 1 (vs_prefix counts a zero as 1).
+// a range envelope 2 jobs, a consistency envelope its k - 1, everything else 1 (vs_prefix counts a zero as 1).  The rule itself, for an
+// envelope of `len` bytes at `env` whose scheme byte the caller has read (a container's inner envelope: composite_impl.inc):
+ZKP_HD inline uint32_t ve_scheme_weight(uint8_t scheme, const uint8_t* env, uint64_t len) { return scheme == 1 ? 2u : scheme == 6 ? ve_consistency_jobs(env, len) : 1u; }
+// ... and for envelope i of a packed list, 1 when its offsets run backwards, leave the blob or span no scheme byte
 ZKP_HD inline uint32_t ve_weight(const uint8_t* blob, const uint64_t* off, uint64_t n, uint64_t i) {
     const uint64_t lo = off[i], hi = off[i + 1];
     if (hi < lo || lo < off[0] || hi > off[n] || hi - lo < 2) return 1;
-    const uint8_t s = blob[lo + 1];
-    return s == 1 ? 2u : s == 6 ? ve_consistency_jobs(blob + lo, hi - lo) : 1u;
+    return ve_scheme_weight(blob[lo + 1], blob + lo, hi - lo);
 }
 
 }  // namespace zkp

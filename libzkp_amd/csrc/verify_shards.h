@@ -72,5 +72,18 @@ ZKP_HD inline uint32_t vs_participants(uint32_t caller, uint32_t shards, const u
     for (uint32_t k = 0; k < shards; k++) { const uint32_t s = (caller + k) % shards; if (!holds || holds[s]) out[m++] = s; }
     return m;
 }
+// The fan-out data of a call over a list whose items hold envelopes of any scheme (the mixed verifier's list, the statements call's, a list of
+// composite containers), one rule for the three: prefix = vs_prefix of the n weights (n + 1 entries); holds[s] = 1 iff shard s holds a usable
+// key of every Groth16 circuit the list needs -- need_eq / need_mem say which, has_key[2 * s + kind] (kind 0: equality, 1: membership) what
+// shard s holds; a kind that is not needed is not looked at, so a list without Groth16 work leaves every shard in; unit = 0 (the prefix sums
+// carry the weights); min_jobs = the larger of the two batch-check thresholds in force, so every slice still takes the one-check path of
+// whichever verifier its envelopes reach.
+ZKP_HD inline void vs_list_fanout(uint64_t n, const uint32_t* weights, bool need_eq, bool need_mem, uint32_t shards, const uint8_t* has_key, uint64_t bp_min, uint64_t g16_min,
+                                  uint64_t* prefix, uint8_t* holds, uint32_t* unit, uint64_t* min_jobs) {
+    vs_prefix(n, weights, prefix);
+    for (uint32_t s = 0; s < shards; s++) holds[s] = (!need_eq || has_key[2 * s]) && (!need_mem || has_key[2 * s + 1]) ? 1 : 0;
+    *unit = 0;
+    *min_jobs = bp_min > g16_min ? bp_min : g16_min;
+}
 
 }  // namespace zkp

@@ -54,25 +54,13 @@ __global__ void __launch_bounds__(256) k_vst_apply(VenvView V, uint8_t* ok, uint
 
 namespace {
 
-// added to the bound shard's counters when a call or slice returns, whichever way
-struct StmtTally {
-    Device& d; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    uint64_t envelopes = 0, refused_envelope = 0, refused_statement = 0, refused_proof = 0;
-    explicit StmtTally(Device& dv) : d(dv) {}
-    ~StmtTally() {
-        Device::StatementsCounter& C = d.statements;
-        C.envelopes += envelopes; C.refused_envelope += refused_envelope; C.refused_statement += refused_statement; C.refused_proof += refused_proof;
-        C.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
 // The call on device pointers, on the bound shard.  max_eq / max_mem: how many of the n ops are equality / membership ops at the most (the
 // host-buffer form counts them, the device form knows only n): the capacity of the index lists and the bound of the bind kernels' grids.  A
 // bind kernel is not launched when its bound is 0.  ok_host (may be null) receives the verdicts, why_host (may be null) the reasons.
 int verify_statements_core(uint64_t n, const zkp_hip_op* d_ops, const uint64_t* d_lists, uint64_t n_lists, const uint8_t* d_blob, const uint64_t* d_off,
                            uint8_t* d_ok, uint8_t* ok_host, uint8_t* d_why, uint8_t* why_host, uint64_t max_eq, uint64_t max_mem) {
-    StmtTally tally(dev());
-    tally.envelopes = n;
+    Tally tally(dev().counters, FAM_STATEMENTS);          // added when the call or slice returns, whichever way
+    tally[CTR_STMT_ENVELOPES] = n;
     hipStream_t st = dev().stream;
     int rc;
     if (max_eq && (rc = ensure_mimc_dev())) return rc;
@@ -105,43 +93,39 @@ int verify_statements_core(uint64_t n, const zkp_hip_op* d_ops, const uint64_t* 
     });
     for (const VenvRecord& r : rec) {
         if (r.scheme) continue;
-        if (r.reserved == ZKP_STMT_STATEMENT) tally.refused_statement++; else tally.refused_envelope++;
+        tally[r.reserved == ZKP_STMT_STATEMENT ? CTR_STMT_REFUSED_STATEMENT : CTR_STMT_REFUSED_ENVELOPE]++;
     }
     if (rc) return rc;
-    if (ok_host) for (uint64_t i = 0; i < n; i++) if (rec[i].scheme && !ok_host[i]) tally.refused_proof++;
+    if (ok_host) for (uint64_t i = 0; i < n; i++) if (rec[i].scheme && !ok_host[i]) tally[CTR_STMT_REFUSED_PROOF]++;
     return 0;
 }
 
-// The host-buffer form on the bound shard, for the m ops at `ops` and the m envelopes whose offsets start at `off` (m + 1 entries): the bytes
-// the envelopes span, their offsets re-based to that span, the ops re-based to the span of lists they name, and that span; then the core.
+// The host-buffer form on the bound shard, for the m ops at `ops` and the m envelopes whose offsets start at `off` (m + 1 entries): the
+// envelopes' span (SpanUpload), the ops re-based to the span of lists they name, and that span; then the core.
 int verify_statements_host(uint64_t m, const zkp_hip_op* ops, const uint64_t* lists, uint64_t n_lists, const uint8_t* blob, const uint64_t* off, uint8_t* ok, uint8_t* why) {
-    if (off[m] < off[0]) {          // no envelope lies inside an empty span
+    SpanUpload up; bool empty;
+    int rc = up.open(m, blob, off, &empty);
+    if (rc) return rc;
+    if (empty) {
         memset(ok, 0, m);
         if (why) memset(why, ZKP_STMT_ENVELOPE, m);
-        StmtTally tally(dev()); tally.envelopes = m; tally.refused_envelope = m;
+        Tally tally(dev().counters, FAM_STATEMENTS); tally[CTR_STMT_ENVELOPES] = m; tally[CTR_STMT_REFUSED_ENVELOPE] = m;
         return 0;
     }
-    const uint64_t first = off[0], bytes = off[m] - first;
-    std::vector<uint64_t> rel(m + 1);
-    for (uint64_t i = 0; i <= m; i++) rel[i] = off[i] - first;
     std::vector<zkp_hip_op> sliced(m);
     const VstListSpan span = vst_slice_ops(m, ops, n_lists, sliced.data());
     uint64_t max_eq = 0, max_mem = 0;
     for (const zkp_hip_op& o : sliced) { max_eq += op_kind(o) == ZKP_HIP_OP_EQUALITY; max_mem += op_kind(o) == ZKP_HIP_OP_MEMBERSHIP; }
     hipStream_t st = dev().stream;
-    DevScope mem;
-    uint8_t *d_blob = nullptr, *d_ok = nullptr; uint64_t *d_off = nullptr, *d_lists = nullptr; zkp_hip_op* d_ops = nullptr;
-    HIP_TRY(mem.alloc(&d_blob, bytes)); HIP_TRY(mem.alloc(&d_off, 8 * (m + 1))); HIP_TRY(mem.alloc(&d_ok, m));
-    HIP_TRY(mem.alloc(&d_ops, sizeof(zkp_hip_op) * m)); HIP_TRY(mem.alloc(&d_lists, 8 * span.count));
-    if (bytes) HIP_TRY(hipMemcpyAsync(d_blob, blob + first, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), 8 * (m + 1), hipMemcpyHostToDevice, st));
+    uint64_t* d_lists = nullptr; zkp_hip_op* d_ops = nullptr;
+    HIP_TRY(up.mem.alloc(&d_ops, sizeof(zkp_hip_op) * m)); HIP_TRY(up.mem.alloc(&d_lists, 8 * span.count));
     HIP_TRY(hipMemcpyAsync(d_ops, sliced.data(), sizeof(zkp_hip_op) * m, hipMemcpyHostToDevice, st));
     if (span.count) HIP_TRY(hipMemcpyAsync(d_lists, lists + span.lo, 8 * span.count, hipMemcpyHostToDevice, st));
-    return verify_statements_core(m, d_ops, d_lists, span.count, d_blob, d_off, d_ok, ok, nullptr, why, max_eq, max_mem);
+    return verify_statements_core(m, d_ops, d_lists, span.count, up.d_blob, up.d_off, up.d_ok, ok, nullptr, why, max_eq, max_mem);
 }
 
-// The fan-out data of the host-buffer form (verify_call): the mixed verifier's (verify_envelopes_plan: ve_weight, the larger of the two
-// batch-check thresholds), but for the keys: a shard takes part when it holds a usable key of every Groth16 circuit of which the list has ops.
+// The fan-out data of the host-buffer form (verify_call): the mixed verifier's weights (ve_weight) through list_fanout (venv_impl.inc), but for
+// the keys: a shard takes part when it holds a usable key of every Groth16 circuit of which the list has ops.
 int verify_statements_plan(uint64_t n, const zkp_hip_op* ops, const uint8_t* blob, const uint64_t* off, const std::vector<Device*>& shards, VerifyFanout& F) {
     std::vector<uint32_t> weights(n);
     bool need[2] = {false, false};
@@ -150,15 +134,7 @@ int verify_statements_plan(uint64_t n, const zkp_hip_op* ops, const uint8_t* blo
         if (op_kind(ops[i]) == ZKP_HIP_OP_EQUALITY) need[G16_EQUALITY] = true;
         if (op_kind(ops[i]) == ZKP_HIP_OP_MEMBERSHIP) need[G16_MEMBERSHIP] = true;
     }
-    F.prefix.resize(n + 1);
-    vs_prefix(n, weights.data(), F.prefix.data());
-    for (Device* d : shards) {
-        bool has = true;
-        for (int kind : {G16_EQUALITY, G16_MEMBERSHIP}) if (need[kind]) has = has && g16_shard_holds_vk(d, kind);
-        F.holds.push_back(has);
-    }
-    F.unit = 0; F.min_jobs = std::max(bp_min_slice(), g16_min_slice());
-    return 0;
+    return list_fanout(weights, need, shards, F);
 }
 
 }  // namespace
@@ -170,7 +146,7 @@ int zkp_stmt_verify(uint64_t n, const zkp_hip_op* ops, const uint64_t* lists, ui
     int rc = check_batch_size(n);
     if (rc) return rc;
     if (!ops || !off || !ok || (!lists && n_lists)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
-    if (!blob && off[n] > off[0]) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
+    if (null_blob_of_span(blob, off, n)) return fail(ZKP_HIP_E_ARGUMENT, "null pointer argument");
     return verify_call(n, [&](const std::vector<Device*>& shards, VerifyFanout& F) { return verify_statements_plan(n, ops, blob, off, shards, F); },
                        [&](uint64_t lo, uint64_t m) { return verify_statements_host(m, ops + lo, lists, n_lists, blob, off + lo, ok + lo, why ? why + lo : nullptr); });
 } ZKP_API_CATCH_INT
@@ -187,21 +163,7 @@ int zkp_stmt_verify_device(uint64_t n, const zkp_hip_op* d_ops, const uint64_t* 
 } ZKP_API_CATCH_INT
 
 int zkp_stmt_counters(double* ms, uint64_t* envelopes, uint64_t* refused_envelope, uint64_t* refused_statement, uint64_t* refused_proof, int reset) try {
-    std::vector<Device*> shards;
-    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
-    Device::StatementsCounter T;
-    for (Device* d : shards) {
-        std::lock_guard<std::mutex> dl(d->mu);
-        Device::StatementsCounter& C = d->statements;
-        T.ms += C.ms; T.envelopes += C.envelopes; T.refused_envelope += C.refused_envelope; T.refused_statement += C.refused_statement; T.refused_proof += C.refused_proof;
-        if (reset) C = Device::StatementsCounter();
-    }
-    if (ms) *ms = T.ms;
-    if (envelopes) *envelopes = T.envelopes;
-    if (refused_envelope) *refused_envelope = T.refused_envelope;
-    if (refused_statement) *refused_statement = T.refused_statement;
-    if (refused_proof) *refused_proof = T.refused_proof;
-    return 0;
+    return read_counters(FAM_STATEMENTS, ms, {envelopes, refused_envelope, refused_statement, refused_proof}, reset);
 } ZKP_API_CATCH_INT
 
 }  // extern "C"

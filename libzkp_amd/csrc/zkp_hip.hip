@@ -41,6 +41,7 @@
 #include "batch_plan.h"
 #include "prover_plan.h"
 #include "verify_shards.h"
+#include "shard_counters.h"
 #include "venv_steps.h"
 #include "composite_steps.h"
 #include "composite_seal.h"
@@ -366,24 +367,9 @@ struct Device {
         double ms = 0; uint64_t launches = 0, adds = 0;
     };
     KProf prof[3];                      // ZKP_HIP_KERNEL_MSM_ED25519 / _BN254_G1 / _BN254_G2
-    // The host-side counters of zkp_hip_profile_read_kernel, always counted: counter `which` is host[which - ZKP_HIP_COUNTER_G16_VERIFY] (counter()).
-    //   _G16_VERIFY        a: segment checks, b: envelopes verified one by one after batch checks that did not stand; ms: host time of those calls (G16VerifyTally)
-    //   _BATCH_SELF_CHECK  a: ops verified, b: ops refused by the self-check of flagged batches; ms: host time from the end of proving (self_check_shard)
-    //   _VERIFY_FANOUT     a: slices of fanned-out verify calls run on this shard, b: their envelopes; ms: host time of those calls, on the caller's shard (verify_fan_out)
-    //   _VERIFY_MIXED      a: scheme passes run by the mixed verifier on this shard, b: envelopes that got a row; ms: host time of its calls (verify_envelopes_core)
-    struct HostCounter { double ms = 0; uint64_t a = 0, b = 0; };
-    HostCounter host[ZKP_HIP_COUNTER_VERIFY_MIXED - ZKP_HIP_COUNTER_G16_VERIFY + 1];
-    HostCounter& counter(int which) { return host[which - ZKP_HIP_COUNTER_G16_VERIFY]; }
-    // zkp_hip_bp_localise_counters (libzkp_hip_bp_localise.h): what the Bulletproofs verifiers did after batch checks that did not stand (BpLocaliseTally)
-    struct BpLocaliseCounter { double ms = 0; uint64_t failed_checks = 0, segment_checks = 0, jobs_again = 0; } bp_localise;
-    // zkp_hip_composites_counters (libzkp_hip_composites.h): what zkp_hip_verify_composites did on this shard (CompTally)
-    struct CompositesCounter { double ms = 0; uint64_t composites = 0, malformed = 0, envelopes = 0; } composites;
-    // libzkp_seal_counters (libzkp_hip_seal.h): what libzkp_seal_composites / _batch did on this shard (SealTally)
-    struct SealCounter { double ms = 0; uint64_t containers = 0, sealed = 0, envelopes = 0, bytes = 0; } seal;
-    // zkp_stmt_counters (libzkp_hip_statements.h): what zkp_stmt_verify / _device did on this shard (StmtTally)
-    struct StatementsCounter { double ms = 0; uint64_t envelopes = 0, refused_envelope = 0, refused_statement = 0, refused_proof = 0; } statements;
-    // zkpkeycheck_counters (libzkp_hip_keycheck.h): the key loader's checks and zkpkeycheck_key on this shard (g16_impl.inc)
-    struct KeyCheckCounter { double ms = 0; uint64_t loads_checked = 0, entries_checked = 0, refused = 0; } keycheck;
+    // The host-side counters, always counted: every family the exports read (shard_counters.h: the family table, Tally, counters_read; read_counters below).
+    // The families of zkp_hip_profile_read_kernel: counter `which` is family which - ZKP_HIP_COUNTER_G16_VERIFY.
+    ShardCounters counters;
     uint64_t stark_verify_resident = 0; // envelopes in the k_stark_verify workgroups this GPU holds at once (asked once: stark_impl.inc)
     struct Trace* trace = nullptr;      // ZKP_HIP_TRACE=<file>: a timeline of every launch of a mixed batch (tools/trace_timeline.py)
     struct ShardWorker* worker = nullptr;      // the host thread that drives this shard in multi-shard calls (created on first use, parked between calls)
@@ -897,16 +883,16 @@ template <class F> int verify_fan_out(const std::vector<Device*>& shards, const 
     const uint32_t count = vs_plan(n, prefix, unit, np, forced > 0 ? (uint64_t)forced : min_jobs, bounds);
     if (count < 2) return 0;
     *fanned = true;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();          // (no Tally: the slices count on their shards, the time on the caller's, after them)
     std::vector<Device*> devs(count);
     for (uint32_t k = 0; k < count; k++) devs[k] = shards[part[k]];
     const int rc = for_each_device(devs, [&](size_t k) {
-        Device::HostCounter& T = dev().counter(ZKP_HIP_COUNTER_VERIFY_FANOUT);
-        T.a++; T.b += bounds[k + 1] - bounds[k];
+        ShardCounter& T = dev().counters[FAM_VERIFY_FANOUT];
+        T.v[CTR_FANOUT_SLICES]++; T.v[CTR_FANOUT_ENVELOPES] += bounds[k + 1] - bounds[k];
         return slice(bounds[k], bounds[k + 1] - bounds[k]);
     });
     std::lock_guard<std::mutex> lk(devs[0]->mu);
-    devs[0]->counter(ZKP_HIP_COUNTER_VERIFY_FANOUT).ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    devs[0]->counters[FAM_VERIFY_FANOUT].ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }
 
@@ -943,6 +929,27 @@ struct EnvelopeUpload {
         HIP_TRY(hipMemcpyAsync(d_len, lens, 4 * n, hipMemcpyHostToDevice, st));
         if (p0) HIP_TRY(hipMemcpyAsync(d_p0, p0, 8 * n, hipMemcpyHostToDevice, st));
         if (p1) HIP_TRY(hipMemcpyAsync(d_p1, p1, 8 * n, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
+// The m envelopes whose offsets start at `off` (m + 1 entries) from host memory on the bound shard's stream: one upload of the bytes they span
+// and of their offsets re-based to that span; d_ok is m bytes for the verdicts.  *empty = true and nothing done when the span is empty (no
+// envelope lies inside one): the caller gives its own answer.  `mem` owns the blocks, and what else the caller takes from it, until this
+// object goes out of scope; `rel` is read by the upload until the stream has passed it.
+struct SpanUpload {
+    DevScope mem;
+    std::vector<uint64_t> rel;
+    uint8_t *d_blob = nullptr, *d_ok = nullptr; uint64_t* d_off = nullptr;
+    int open(uint64_t m, const uint8_t* blob, const uint64_t* off, bool* empty) {
+        if ((*empty = off[m] < off[0])) return 0;
+        const uint64_t first = off[0], bytes = off[m] - first;
+        // (an offset below `first` wraps to a value beyond `bytes`, so the classification rejects its envelope as outside the span)
+        rel.resize(m + 1);
+        for (uint64_t i = 0; i <= m; i++) rel[i] = off[i] - first;
+        hipStream_t st = dev().stream;
+        HIP_TRY(mem.alloc(&d_blob, bytes)); HIP_TRY(mem.alloc(&d_off, 8 * (m + 1))); HIP_TRY(mem.alloc(&d_ok, m));
+        if (bytes) HIP_TRY(hipMemcpyAsync(d_blob, blob + first, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_off, rel.data(), 8 * (m + 1), hipMemcpyHostToDevice, st));
         return 0;
     }
 };
@@ -1159,8 +1166,24 @@ int prover_args(std::vector<uint8_t>& fresh, const uint8_t*& seeds, uint64_t n, 
     seeds = fresh.data();
     return 0;
 }
+// a packed list (n items, n + 1 offsets): a null blob is an argument error unless the offsets span nothing
+bool null_blob_of_span(const void* blob, const uint64_t* off, uint64_t n) { return !blob && off[n] > off[0]; }
+// One family of the host-side counters summed over every registered shard (shard_counters.h: counters_read), each shard read -- and zeroed,
+// when `reset` -- under its own lock; the registry lock is not held while a shard's is taken (Bind::open takes them in the other order).
+// Needs no device.  The body of the five *_counters exports and of zkp_hip_profile_read_kernel for the ids that are not kernels.
+int read_counters(uint32_t family, double* ms, std::initializer_list<uint64_t*> outs, int reset) {
+    std::vector<Device*> shards;
+    { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
+    std::vector<ShardCounters*> tables; std::vector<std::mutex*> locks;
+    for (Device* d : shards) { tables.push_back(&d->counters); locks.push_back(&d->mu); }
+    counters_read(tables.data(), locks.data(), shards.size(), family, reset != 0, ms, outs);
+    return 0;
+}
 // a verifier's: envelopes of `stride` bytes, zero refused
 int verifier_args(uint64_t n, std::initializer_list<const void*> ptrs, uint64_t stride) { return host_args(n, ptrs, nullptr, stride, 1, "bad stride"); }
+
+static_assert(FAM_G16_VERIFY == 0 && FAM_VERIFY_MIXED == ZKP_HIP_COUNTER_VERIFY_MIXED - ZKP_HIP_COUNTER_G16_VERIFY && FAM_BATCH_SELF_CHECK == ZKP_HIP_COUNTER_BATCH_SELF_CHECK - ZKP_HIP_COUNTER_G16_VERIFY &&
+              FAM_VERIFY_FANOUT == ZKP_HIP_COUNTER_VERIFY_FANOUT - ZKP_HIP_COUNTER_G16_VERIFY, "shard_counters.h: the id-based families sit at which - ZKP_HIP_COUNTER_G16_VERIFY");
 
 }  // namespace
 // the ed25519 sum launcher under an external name (edg_launch.h): launch_sum_ed above has internal linkage
@@ -1245,12 +1268,7 @@ void zkp_hip_shutdown(void) try {
         for (auto& F : d->fam) { free_set(F.p1); for (auto& s : F.rd) free_set(s); F.ready = false; }
         trace_release();
         for (auto& K : d->prof) { for (auto& e : K.ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } K = Device::KProf(); }
-        for (auto& C : d->host) C = Device::HostCounter();
-        d->bp_localise = Device::BpLocaliseCounter();
-        d->composites = Device::CompositesCounter();
-        d->statements = Device::StatementsCounter();
-        d->seal = Device::SealCounter();
-        d->keycheck = Device::KeyCheckCounter();
+        d->counters = ShardCounters();
         d->stark_verify_resident = 0;
         (void)hipStreamDestroy(d->stream); d->stream = nullptr;
         d->ready = false; d->bp_ready = false; d->profiling = false; d->max_chunks = 0; d->next_slot = 0; d->generation++;
@@ -1267,17 +1285,12 @@ void zkp_hip_profile_enable(int on) try {
 // accumulated over all shards
 int zkp_hip_profile_read_kernel(int which, double* ms, uint64_t* launches, uint64_t* point_adds, int reset) try {
     if (which < 0 || which > ZKP_HIP_COUNTER_VERIFY_MIXED) return fail(ZKP_HIP_E_ARGUMENT, "unknown kernel id");
+    // host-side counters: no events to collect, and a shard that has not run yet is not initialised for them
+    if (which >= ZKP_HIP_COUNTER_G16_VERIFY) return read_counters(which - ZKP_HIP_COUNTER_G16_VERIFY, ms, {launches, point_adds}, reset);
     std::vector<Device*> shards;
     { Registry& R = registry(); std::lock_guard<std::mutex> lk(R.mu); shards = R.shards; }
     double tms = 0; uint64_t tl = 0, ta = 0;
     for (Device* d : shards) {
-        if (which >= ZKP_HIP_COUNTER_G16_VERIFY) {          // host-side counters: no events to collect, and a shard that has not run yet is not initialised for them
-            std::lock_guard<std::mutex> dl(d->mu);
-            Device::HostCounter& C = d->counter(which);
-            tms += C.ms; tl += C.a; ta += C.b;
-            if (reset) C = Device::HostCounter();
-            continue;
-        }
         Bind bind; int rc = bind.open(d);
         if (rc) return rc;
         HIP_TRY(hipDeviceSynchronize());

@@ -16,6 +16,8 @@ void emul_ve_classify(uint64_t n, const uint8_t* blob, const uint64_t* off, cons
 }
 uint32_t emul_ve_consistency_jobs(const uint8_t* env, uint64_t len) { return ve_consistency_jobs(env, len); }
 uint32_t emul_ve_weight(const uint8_t* blob, const uint64_t* off, uint64_t n, uint64_t i) { return ve_weight(blob, off, n, i); }
+// the rule behind it, as a container's inner envelope reaches it: the scheme byte the caller read, the envelope, its length
+uint32_t emul_ve_scheme_weight(uint32_t scheme, const uint8_t* env, uint64_t len) { return ve_scheme_weight((uint8_t)scheme, env, len); }
 // the plan of n records: out = rows[7] row0[7] stride[7] base[7] total_rows live bytes (31 u64); returns ve_plan's code
 uint32_t emul_ve_plan(uint64_t n, const uint8_t* rec, uint32_t* op_row, uint64_t* out) {
     VenvPlan P;

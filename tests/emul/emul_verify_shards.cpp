@@ -17,6 +17,13 @@ uint32_t emul_vs_plan_weighted(uint64_t n, const uint32_t* weights, uint32_t sha
     return vs_plan(n, prefix_out, 0, shards, min_jobs, bounds);
 }
 uint32_t emul_vs_participants(uint32_t caller, uint32_t shards, const uint8_t* holds, uint32_t* out) { return vs_participants(caller, shards, holds, out); }
+// the fan-out data of a list call: prefix (n + 1), holds (shards), out = {unit, min_jobs}; has_key is [shards][2] (equality, membership)
+void emul_vs_list_fanout(uint64_t n, const uint32_t* weights, int need_eq, int need_mem, uint32_t shards, const uint8_t* has_key, uint64_t bp_min, uint64_t g16_min,
+                         uint64_t* prefix, uint8_t* holds, uint64_t* out) {
+    uint32_t unit = 99; uint64_t min_jobs = 0;
+    vs_list_fanout(n, weights, need_eq != 0, need_mem != 0, shards, has_key, bp_min, g16_min, prefix, holds, &unit, &min_jobs);
+    out[0] = unit; out[1] = min_jobs;
+}
 }
 
 namespace {
@@ -65,6 +72,17 @@ int main() {
     EXPECT(vs_participants(2, 4, holds, out) == 3 && out[0] == 2 && out[1] == 3 && out[2] == 0);
     EXPECT(vs_participants(1, 4, holds, out) == 0 && vs_participants(4, 4, holds, out) == 0);
     EXPECT(vs_participants(0, 2, nullptr, out) == 2 && out[0] == 0 && out[1] == 1);
+    // the list calls' fan-out data: every combination of needed keys against four shards that hold both, equality only, membership only, none
+    const uint8_t has_key[8] = {1, 1, 1, 0, 0, 1, 0, 0};
+    const uint32_t lw[5] = {2, 0, 1, 4, 1};
+    for (int need = 0; need < 4; need++) for (uint64_t a : {4096ull, 8193ull}) for (uint64_t b : {4096ull, 8193ull}) {
+        uint64_t prefix[6], want[6], min_jobs = 0; uint8_t lh[4] = {9, 9, 9, 9}; uint32_t unit = 9;
+        vs_list_fanout(5, lw, (need & 1) != 0, (need & 2) != 0, 4, has_key, a, b, prefix, lh, &unit, &min_jobs);
+        vs_prefix(5, lw, want);
+        for (int i = 0; i < 6; i++) EXPECT(prefix[i] == want[i]);
+        EXPECT(prefix[5] == 9 && unit == 0 && min_jobs == (a > b ? a : b));
+        for (int s = 0; s < 4; s++) EXPECT(lh[s] == (((need & 1) == 0 || has_key[2 * s]) && ((need & 2) == 0 || has_key[2 * s + 1]) ? 1 : 0));
+    }
     if (failures) { std::fprintf(stderr, "emul_verify_shards: %d failure(s)\n", failures); return 1; }
     std::printf("emul_verify_shards ok\n");
     return 0;

@@ -24,6 +24,8 @@ def lib():
     L.emul_ve_classify.restype = None
     L.emul_ve_consistency_jobs.argtypes = [VP, U64]
     L.emul_ve_weight.argtypes = [VP, VP, U64, U64]
+    L.emul_ve_scheme_weight.argtypes = [U32, VP, U64]
+    L.emul_ve_scheme_weight.restype = U32
     L.emul_ve_plan.argtypes = [U64, VP, VP, VP]
     L.emul_ve_plan_uniform.argtypes = [U64, U32, U32]
     L.emul_ve_copy.argtypes = [VP, VP, U32, VP, VP, U32]
@@ -218,6 +220,31 @@ def test_the_consistency_job_rule_is_the_one_the_verifier_reads(lib):
     env = np.zeros(16, dtype=np.uint8)
     env[10:14] = np.frombuffer(((1 << 20) - 1).to_bytes(4, "little"), dtype=np.uint8)
     assert lib.emul_ve_consistency_jobs(P(env), 1 << 30) == (1 << 20) - 2 and lib.emul_ve_consistency_jobs(P(env), 1 << 20) == 0
+
+
+def test_the_weight_rule_is_one_for_a_packed_list_and_for_a_containers_envelopes(lib):
+    """ve_weight (envelope i of a packed list: the mixed verifier's and the statements call's fan-out) and ve_scheme_weight (scheme byte,
+    envelope, length: a container's inner envelopes) give the same weight: 2 for a range envelope, k - 1 for a consistency envelope that
+    holds what its k announces and 0 for one that does not, 1 for everything else, scheme bytes that name no scheme included"""
+    rng = np.random.default_rng(21)
+
+    def consistency(k, short=0):
+        need = 4 + 32 * k + (4 + 672 + 32) * max(k - 1, 0)
+        return make_env(rng, 6, payload=k.to_bytes(4, "little") + bytes(need - 4 - short))
+
+    envs = [make_env(rng, s, payload=bytes(40)) for s in (0, 1, 2, 3, 4, 5, 7, 255)]
+    envs += [consistency(1), consistency(2), consistency(5), consistency(5, short=1), consistency(0), make_env(rng, 6, payload=b"")]
+    want = [1, 2, 1, 1, 1, 1, 1, 1, 0, 1, 4, 0, 0, 0]
+    blob = np.frombuffer(b"".join(envs) + b"\0", dtype=np.uint8)
+    off = np.concatenate(([0], np.cumsum([len(e) for e in envs]))).astype(np.uint64)
+    for i, (e, w) in enumerate(zip(envs, want)):
+        one = np.frombuffer(e + b"\0", dtype=np.uint8)
+        assert w == (2 if e[1] == 1 else ref_jobs(e) if e[1] == 6 else 1)
+        assert lib.emul_ve_weight(P(blob), P(off), len(envs), i) == w == lib.emul_ve_scheme_weight(e[1], P(one), len(e)), i
+    # what only the packed form can meet: an envelope too short to hold a scheme byte weighs 1, whatever lies behind it
+    two = np.frombuffer(bytes([2]) + envs[1], dtype=np.uint8)
+    assert lib.emul_ve_weight(P(two), P(np.array([0, 1, len(two)], dtype=np.uint64)), 2, 0) == 1
+    assert lib.emul_ve_weight(P(two), P(np.array([0, 1, len(two)], dtype=np.uint64)), 2, 1) == 2
 
 
 # ---- the copy

@@ -20,6 +20,8 @@ def lib():
     L.emul_vs_plan_uniform.argtypes = [U64, ctypes.c_uint32, ctypes.c_uint32, U64, ctypes.c_void_p]
     L.emul_vs_plan_weighted.argtypes = [U64, ctypes.c_void_p, ctypes.c_uint32, U64, ctypes.c_void_p, ctypes.c_void_p]
     L.emul_vs_participants.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    L.emul_vs_list_fanout.argtypes = [U64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, U64, U64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.emul_vs_list_fanout.restype = None
     for f in (L.emul_vs_plan_uniform, L.emul_vs_plan_weighted, L.emul_vs_participants, L.emul_vs_max_shards):
         f.restype = ctypes.c_uint32
     return L
@@ -157,6 +159,56 @@ def test_participants(lib):
     assert part(2, [1, 0, 1, 1]) == [2, 3, 0]                       # registration order, starting with the caller's
     assert part(1, [1, 0, 1, 1]) == []                              # the caller's shard holds none: the call stays put and fails as it always has
     assert part(0, [1]) == [0]
+
+
+# ---- the fan-out data of the calls over a list of envelopes of any scheme (vs_list_fanout): the mixed verifier's, the statements call's, the composites call's
+def list_fanout(L, weights, need_eq, need_mem, has_key, bp_min=4096, g16_min=8193):
+    """-> (prefix, holds, unit, min_jobs); has_key: per shard (equality, membership)"""
+    w = np.asarray(weights, dtype=np.uint32)
+    k = np.asarray(has_key, dtype=np.uint8).reshape(-1, 2)
+    prefix, holds, out = np.full(len(w) + 2, 2**64 - 1, dtype=np.uint64), np.full(len(k) + 1, 77, dtype=np.uint8), np.full(2, 2**64 - 1, dtype=np.uint64)
+    L.emul_vs_list_fanout(len(w), P(w), int(need_eq), int(need_mem), len(k), P(k), bp_min, g16_min, P(prefix), P(holds), P(out))
+    assert prefix[-1] == 2**64 - 1 and holds[-1] == 77                                               # n + 1 sums and one flag per shard, no more
+    return [int(x) for x in prefix[:-1]], [int(x) for x in holds[:-1]], int(out[0]), int(out[1])
+
+
+KEYS = [(1, 1), (1, 0), (0, 1), (0, 0)]                                                              # four shards: both keys, equality only, membership only, none
+
+
+def test_list_fanout_without_groth16_work_leaves_every_shard_in(lib):
+    prefix, holds, unit, min_jobs = list_fanout(lib, [2, 1, 1], False, False, KEYS)
+    assert holds == [1, 1, 1, 1] and prefix == [0, 2, 3, 4] and unit == 0 and min_jobs == 8193
+    assert list_fanout(lib, [2, 1, 1], False, False, [(0, 0)] * 3)[1] == [1, 1, 1]
+
+
+def test_list_fanout_keeps_only_the_shards_that_hold_every_needed_key(lib):
+    assert list_fanout(lib, [1], True, False, KEYS)[1] == [1, 1, 0, 0]                               # equality needed
+    assert list_fanout(lib, [1], False, True, KEYS)[1] == [1, 0, 1, 0]                               # membership needed: the other column of the table
+    assert list_fanout(lib, [1], True, True, KEYS)[1] == [1, 0, 0, 0]                                # both
+    assert list_fanout(lib, [1], True, True, [(1, 1)] * 64)[1] == [1] * 64
+    assert list_fanout(lib, [1], True, True, [])[1] == []
+
+
+def test_list_fanout_a_caller_without_the_key_keeps_the_call(lib):
+    holds = np.asarray(list_fanout(lib, [1] * 10, True, False, [(0, 1), (1, 1), (1, 0)])[1], dtype=np.uint8)
+    assert holds.tolist() == [0, 1, 1]
+    out = np.zeros(8, dtype=np.uint32)
+    assert lib.emul_vs_participants(0, 3, P(holds), P(out)) == 0                                     # vs_participants, unchanged: the call stays put and fails as it always has
+    assert lib.emul_vs_participants(1, 3, P(holds), P(out)) == 2 and out[:2].tolist() == [1, 2]
+
+
+def test_list_fanout_counts_zero_weights_as_one_and_takes_the_larger_threshold(lib):
+    prefix, _, unit, _ = list_fanout(lib, [0, 0, 4, 0, 2], False, False, KEYS)
+    assert prefix == [0, 1, 2, 6, 7, 9] and unit == 0                                                # vs_prefix's sums: the plan reads the weights there, not from `unit`
+    assert list_fanout(lib, [], False, False, KEYS)[0] == [0]
+    for bp_min, g16_min in ((4096, 8193), (8193, 4096), (7, 7), (1, 2**40)):
+        assert list_fanout(lib, [1], True, True, KEYS, bp_min, g16_min)[3] == max(bp_min, g16_min)
+    # the plan over these data: 16 384 range envelopes of a mixed list on eight shards cut at 8193 jobs, not at 4096
+    prefix, holds, unit, min_jobs = list_fanout(lib, [2] * 16384, False, False, [(0, 0)] * 8)
+    b = np.zeros(66, dtype=np.uint64)
+    pf = np.asarray(prefix, dtype=np.uint64)
+    count = lib.emul_vs_plan_weighted(16384, P(np.full(16384, 2, dtype=np.uint32)), sum(holds), min_jobs, P(b), P(pf))
+    assert count == 3 and 32768 // 8193 == 3
 
 
 def test_the_program_of_its_own_passes_under_host_sanitizers(tmp_path):
